@@ -22,11 +22,17 @@ bytes (stored qdata + x + y + map) as a lower bound; `alg_ratio` = SURVEY §8(d)
 algorithmic bytes (56 B per quadrature point) / the same time / 8 TB/s, which exceeds 1
 when the compressed (AFFINE) layout stores less than the formula counts.
 
-Beside the timed Mults (outside the timed region), the one-GPU line also carries the same
-run's variants (the reference's numbering, a trilinear mesh, the drop-in configuration, the full
-per-point layout, the Pennes and ex16p coefficient paths), the marginal Jacobi-PCG iteration
-(`pcg_iteration`, the device-driven loop) and one ex16p SDIRK33 step (`sdirk_step`), and the CPU
-oracle baseline.
+A plain run does what the headline figure needs and nothing else: set-up, a clock-settling run of
+untimed Mults, the warm-up, the timed steps, and the result line (metric, value, unit, ms_per_step,
+config).  --dump-outputs DIR writes what the last timed step computed (DIR/y.npy, float64; a fixed
+seeded sample of a larger vector) so that two builds can be compared output for output.
+
+With --full, beside the timed Mults (outside the timed region), the line also carries the
+roofline (a HIP-event pass over the dominant kernel, the measured stream rates) and, on one GPU,
+the same run's variants (the reference's numbering, a trilinear mesh, the drop-in configuration,
+the full per-point layout, the Pennes and ex16p coefficient paths), the marginal Jacobi-PCG
+iteration (`pcg_iteration`, the device-driven loop) and one ex16p SDIRK33 step (`sdirk_step`),
+the re-assembly time and the CPU oracle baseline.
 """
 import argparse
 import importlib.util
@@ -218,13 +224,11 @@ def time_mults(apply, x, y, steps, warmup, world, dist, torch):
     return t1 - t0
 
 
-def kernel_ms(forms, apply, x, y, steps, torch, settle_s=0.06, world=1, dist=None):
-    """HIP events around the dominant (fused apply) kernel(s) of each Mult, on the stream they
-    are launched on (a pass of its own, outside the timed loop); ms per Mult.  It runs right
-    before the timed loop and first keeps the GPU busy for `settle_s` of untimed Mults: after
+def settle(apply, x, y, torch, settle_s=0.06, dist=None):
+    """Keeps the GPU busy for `settle_s` of untimed Mults right before the timed loop: after
     any idle of a few ms the first ~50 Mults run up to 17-30% slower while the power
-    management settles (profiles/r2_ramp_c4.json, r2_ramp_c5.json), so both this pass and the
-    timed steps that follow it see the sustained rate of a PCG loop."""
+    management settles (profiles/r2_ramp_c4.json, r2_ramp_c5.json), so the timed steps (and
+    the kernel-timing pass of --full) see the sustained rate of a PCG loop."""
     # the settle count is rank 0's and identical on every rank: a distributed Mult is collective
     for _ in range(4):
         apply(x, y)
@@ -242,6 +246,13 @@ def kernel_ms(forms, apply, x, y, steps, torch, settle_s=0.06, world=1, dist=Non
         apply(x, y)
         if i % 64 == 63:
             torch.cuda.synchronize()  # bounded host run-ahead; no idle long enough to matter
+
+
+def kernel_ms(forms, apply, x, y, steps, torch, settle_s=0.06, world=1, dist=None):
+    """HIP events around the dominant (fused apply) kernel(s) of each Mult, on the stream they
+    are launched on (a pass of its own, outside the timed loop); ms per Mult.  It runs right
+    before the timed loop, after settle()'s untimed Mults."""
+    settle(apply, x, y, torch, settle_s, dist)
     for f in forms:
         f.timing(True)
     for _ in range(steps):
@@ -251,6 +262,24 @@ def kernel_ms(forms, apply, x, y, steps, torch, settle_s=0.06, world=1, dist=Non
     for f in forms:
         f.timing(False)
     return kms / steps
+
+
+DUMP_MAX_ENTRIES = 1 << 22  # 32 MiB of float64 over all the files of one run
+
+
+def dump_outputs(path, names, vectors, ranks=1):
+    """--dump-outputs: the vectors the last timed Mult wrote, as <path>/<name>.npy (float64).  The
+    files of one run (`ranks` processes) hold at most DUMP_MAX_ENTRIES entries between them: a
+    longer vector is sampled at a fixed set of indices (seeded by its length alone, ascending),
+    the same in every run and every build."""
+    os.makedirs(path, exist_ok=True)
+    cap = max(1, DUMP_MAX_ENTRIES // (len(names) * ranks))
+    for name, v in zip(names, vectors):
+        a = v.detach().cpu().numpy().astype(np.float64, copy=False)
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(a.size).choice(a.size, cap, replace=False))
+            a = a[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 PART_NAME = {"slabs": "z-slabs", "boxes": "boxes", "bricks": "brick runs"}
@@ -462,6 +491,15 @@ def main():
     ap.add_argument("--c3-refine", type=int, default=6,
                     help="c3: uniform refinements of fichera.mesh (6 -> 14.9M DoF, 5 -> 1.88M)")
     ap.add_argument("--kernel", choices=["auto", "tpe", "wpe", "unfused", "line"], default="auto")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, also measure the roofline (HIP-event kernel pass, stream rates), "
+                         "the CPU baseline, the same run's variants, the PCG iteration, the SDIRK step and the "
+                         "re-assembly; --no-cpu-baseline, --full-layout, --variants, --pcg-iters and --sdirk "
+                         "select among these.  Off: only the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the vector the last timed Mult computed as DIR/y.npy "
+                         "(float64; one file per rank or loopback member when partitioned; above 4M entries a "
+                         "fixed seeded sample of them)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--geometry", choices=["compressed", "full"], default="compressed",
@@ -663,7 +701,8 @@ def main():
                 pf.Assemble()
                 forms.append(pf)
             group = E.ParGroup(forms)
-            xs = [torch.empty(f.true_size, dtype=torch.float64, device="cuda").uniform_(-1, 1) for f in forms]
+            xs = [torch.empty(f.true_size, dtype=torch.float64, device="cuda").uniform_(
+                -1, 1, generator=torch.Generator(device="cuda").manual_seed(1 + r)) for r, f in enumerate(forms)]
             ys = [torch.empty_like(v) for v in xs]
             if args.member is not None:
                 member_bench(args, E, torch, group, xs, ys, fes.ndofs, workload, dl)
@@ -678,25 +717,37 @@ def main():
     y = torch.empty_like(x)
     torch.cuda.synchronize()
 
-    dl.at("kernel timing")
     pdist = dist if par else None
     if par:
         dist.barrier()  # all ranks settle together
-    kms = kernel_ms(timed_forms, apply, x, y, args.steps, torch, world=world, dist=pdist)
+    if args.full:
+        dl.at("kernel timing")
+        kms = kernel_ms(timed_forms, apply, x, y, args.steps, torch, world=world, dist=pdist)
+    else:
+        dl.at("settle")
+        settle(apply, x, y, torch, dist=pdist)
+        kms = 0.0
     dl.at("timed Mults")
     dt = time_mults(apply, x, y, args.steps, args.warmup, world, pdist, torch)
+    if args.dump_outputs:
+        dl.at("dump outputs")
+        if nsub > 1 and not par:
+            dump_outputs(args.dump_outputs, [f"y_member{r}" for r in range(nsub)], ys)
+        else:
+            dump_outputs(args.dump_outputs, [f"y_rank{rank}" if world > 1 else "y"], [y], ranks=world)
     abytes = sum(f.algorithmic_bytes() for f in timed_forms)
     nd = (order + 1) ** 3
     mbytes = sum(min_bytes(f, f.part.ne_local if hasattr(f, "part") else fes.ne, nd, f.true_size
                            if hasattr(f, "true_size") else n_true) for f in timed_forms)
     qbytes = sum(f.qdata_bytes() for f in timed_forms)
     layout = qdata_layout(E, timed_forms[0])
-    pcg = c3_pcg(E, torch, fes, form) if args.workload == "c3" else None
-    reasm = reassembly_ms(torch, form) if (form is not None and args.workload != "c3") else None
+    pcg = c3_pcg(E, torch, fes, form) if (args.full and args.workload == "c3") else None
+    reasm = reassembly_ms(torch, form) if (args.full and form is not None and args.workload != "c3") else None
     pcg_it = (pcg_iteration_ms(torch, form, fes.ndofs, args.pcg_iters)
-              if (args.pcg_iters and form is not None and world == 1 and args.loopback <= 1) else None)
+              if (args.full and args.pcg_iters and form is not None and world == 1 and args.loopback <= 1) else None)
     sdirk = (sdirk_step(E, torch, mesh, fes, keep)
-             if (args.sdirk and form is not None and world == 1 and args.loopback <= 1 and args.workload != "c3")
+             if (args.full and args.sdirk and form is not None and world == 1 and args.loopback <= 1
+                 and args.workload != "c3")
              else None)
 
     # aggregate over ranks: total true dofs, max time; kernel ms per Mult (interior + boundary
@@ -717,7 +768,7 @@ def main():
     lattice = timed_forms[0].AddressingInfo()
 
     subs = {}
-    serial_main = not par and args.loopback <= 1 and args.workload != "c3"
+    serial_main = args.full and not par and args.loopback <= 1 and args.workload != "c3"
     if serial_main and args.full_layout and compress:
         dl.at("full layout")
         del apply
@@ -775,10 +826,12 @@ def main():
             del fv
 
     if rank == 0:
-        dl.at("stream copy peak")
-        stream = stream_copy_peak(E, torch)
+        stream = None
+        if args.full:
+            dl.at("stream copy peak")
+            stream = stream_copy_peak(E, torch)
         cpu = None
-        if not args.no_cpu_baseline and not par and args.loopback <= 1:
+        if args.full and not args.no_cpu_baseline and not par and args.loopback <= 1:
             dl.at("cpu baseline")
             cpu = cpu_baseline(fes, mesh, alpha, T, args.cpu_baseline_seconds, args.workload)
         line = {
@@ -811,10 +864,11 @@ def main():
                                 if par else
                                 (f"loopback {PART_NAME[args.partition]} x{args.loopback} on one GPU" if args.loopback > 1 else "single GPU")),
             },
-            "roofline": roofline(args.workload + variant, world, layout, kavg_ms, bytes_total / world,
-                                 mbytes_total / world, stream, use_pin=pin_ok, flops=alg_flops(order, ne_own)),
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            line["roofline"] = roofline(args.workload + variant, world, layout, kavg_ms, bytes_total / world,
+                                        mbytes_total / world, stream, use_pin=pin_ok, flops=alg_flops(order, ne_own))
+            line["cpu_baseline"] = cpu
         if sdirk is not None:
             line["sdirk_step"] = sdirk
         if pcg_it is not None:

@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 for N in "$@"; do
   T=$WL${TAG:+-$TAG}-n$N
   timeout -k 10 300 rocprofv3 --kernel-trace -d "$O/$T" -o run --output-format csv \
-    -- python3 bench.py --workload $WL --loopback $N --steps 30 --warmup 5 --no-cpu-baseline --full-layout 0 ${EXTRA:-} \
+    -- python3 bench.py --workload $WL --loopback $N --steps 30 --warmup 5 --full --no-cpu-baseline --full-layout 0 ${EXTRA:-} \
     > "$O/$T.json" 2> "$O/$T.err" || exit $?
   python3 profiles/rank_trace.py "$O/$T" $N || exit $?
 done

@@ -11,10 +11,10 @@ OUT=${GRAFT_REPO_ROOT:-$(pwd)}/gpurun_out/prof_${TAG}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -T -d "$OUT/trace" -o run --output-format csv \
-  -- python3 bench.py $ARGS --no-cpu-baseline > "$OUT/bench_trace.json"
+  -- python3 bench.py $ARGS --full --no-cpu-baseline > "$OUT/bench_trace.json"
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE -T -d "$OUT/fetch" -o run --output-format csv \
-  -- python3 bench.py $ARGS --no-cpu-baseline > "$OUT/bench_fetch.json"
+  -- python3 bench.py $ARGS --full --no-cpu-baseline > "$OUT/bench_fetch.json"
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE -T -d "$OUT/write" -o run --output-format csv \
-  -- python3 bench.py $ARGS --no-cpu-baseline > "$OUT/bench_write.json"
+  -- python3 bench.py $ARGS --full --no-cpu-baseline > "$OUT/bench_write.json"
 python3 profiles/pmc_reduce.py "$OUT" > "$OUT/pmc_summary.json"
 cat "$OUT/pmc_summary.json"

@@ -11,6 +11,6 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 C=${SQ_COUNTERS:-SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT}
 timeout -s KILL 120 rocprofv3 --pmc $C -T -d "$OUT" -o run --output-format csv \
-  -- python3 bench.py $ARGS --no-cpu-baseline > "$OUT/bench.json"
+  -- python3 bench.py $ARGS --full --no-cpu-baseline > "$OUT/bench.json"
 python3 profiles/sq_reduce.py "$OUT" > "$OUT/sq_summary.json"
 cat "$OUT/sq_summary.json"

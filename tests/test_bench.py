@@ -22,7 +22,8 @@ def test_bench_help_lists_the_options():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], cwd=ROOT, capture_output=True,
                          text=True, timeout=120)
     assert out.returncode == 0
-    for opt in ("--gpus", "--steps", "--warmup", "--workload", "--schedule", "--loopback", "--member", "--deadline"):
+    for opt in ("--gpus", "--steps", "--warmup", "--workload", "--schedule", "--loopback", "--member", "--deadline",
+                "--full", "--dump-outputs"):
         assert opt in out.stdout
 
 
@@ -47,7 +48,7 @@ SMALL = ["--workload", "c2", "--c2-n", "12", "--steps", "3", "--warmup", "1", "-
 
 @pytest.mark.gpu
 def test_bench_single_gpu_line():
-    b = run_bench(*SMALL)
+    b = run_bench(*SMALL, "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in b, k
@@ -78,11 +79,79 @@ def test_bench_single_gpu_line():
     assert b["ex16"]["snapshot"] == {"on": True, "mass_values": 2, "law_at_point": False}
     assert b["pennes"]["qdata_layout"] == b["ex16"]["qdata_layout"] == "affine_tsm"
     assert b["pennes"]["roofline"]["traffic"] is None and b["pennes"]["value"] > 0  # (pins: default size only)
-    s = run_bench(*SMALL, "--variants", "0", "--coefficient-snapshot", "0")
+    s = run_bench(*SMALL, "--full", "--variants", "0", "--coefficient-snapshot", "0")
     assert s["value"] > 0 and "entity_numbering" not in s
     assert b["config"]["qdata_layout"] == "affine_ts" and s["config"]["qdata_layout"] == "affine"
     e = run_bench(*SMALL, "--numbering", "entity", "--variants", "0")
     assert e["config"]["numbering"].startswith("entity") and "entity_numbering" not in e
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def test_dump_outputs_writes_float64_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a vector within the cap is written whole, a longer one at a fixed ascending
+    set of indices (the same in two runs), float64, the cap shared between the files of a run."""
+    import numpy as np
+    import torch
+    b = _bench_module()
+    monkeypatch.setattr(b, "DUMP_MAX_ENTRIES", 1000)
+    v = torch.arange(5000, dtype=torch.float64)
+    w = torch.arange(300, dtype=torch.float64)
+    b.dump_outputs(str(tmp_path / "a"), ["y"], [v])
+    b.dump_outputs(str(tmp_path / "b"), ["y"], [v])
+    ya, yb = np.load(tmp_path / "a" / "y.npy"), np.load(tmp_path / "b" / "y.npy")
+    assert ya.dtype == np.float64 and ya.shape == (1000,) and np.array_equal(ya, yb)
+    assert np.all(np.diff(ya) > 0) and ya.min() >= 0 and ya.max() < 5000  # distinct entries of v, in order
+    b.dump_outputs(str(tmp_path / "c"), ["y_member0", "y_member1"], [v, w])
+    assert np.load(tmp_path / "c" / "y_member0.npy").shape == (500,)
+    assert np.array_equal(np.load(tmp_path / "c" / "y_member1.npy"), w.numpy())
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_output(tmp_path):
+    """A plain run times its steps and nothing else (no kernel-timing pass, stream rates, variants, PCG,
+    SDIRK or CPU baseline: those are --full's), and --dump-outputs writes the vector of its last timed
+    Mult: the bench form applied to the seeded x, reproduced here in another process."""
+    import numpy as np
+    import torch
+    import ecm2_amd as E
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "c2", "--c2-n",
+                          "12", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")], cwd=ROOT,
+                         capture_output=True, text=True, timeout=240)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype",
+              "config"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "MDoF/s" and line["dtype"] == "f64"
+    assert line["value"] == pytest.approx(line["config"]["ndofs"] / (line["ms_per_step"] * 1e-3) / 1e6, rel=1e-3)
+    for k in ("roofline", "cpu_baseline", "pcg_iteration", "sdirk_step", "reassembly_ms", "full_layout",
+              "entity_numbering", "trilinear", "drop_in", "pennes", "ex16"):
+        assert k not in line, k
+    for stage in ("kernel timing", "stream copy peak", "cpu baseline", "full layout"):
+        assert stage not in out.stderr, stage
+    y = np.load(tmp_path / "out" / "y.npy")
+    assert y.dtype == np.float64 and y.shape == (line["config"]["ndofs"],)
+    b = _bench_module()
+    E.load_library()
+    mesh, fes = b.cartesian_space(E, 12, 12, 12, 2, "structured", "affine")
+    keep = []
+    form = b.bench_form(E, torch, mesh, fes, keep)
+    x = torch.empty(fes.ndofs, dtype=torch.float64, device="cuda")
+    x.uniform_(-1.0, 1.0, generator=torch.Generator(device="cuda").manual_seed(1))
+    yr = torch.empty_like(x)
+    form.Mult(x, yr)
+    torch.cuda.synchronize()
+    yr = yr.cpu().numpy()
+    # the same kernel on the same input: at most a reordering of a dof's <= 8 element contributions,
+    # a few FP64 roundings (1.1e-16 each) of the largest entry
+    assert np.abs(y - yr).max() <= 1e-13 * np.abs(yr).max()
 
 
 @pytest.mark.gpu
@@ -95,7 +164,7 @@ def test_bench_loopback_group_and_member_lines():
     assert m["pcg"] is None
     p = run_bench(*SMALL, "--loopback", "2", "--member", "-1", "--pcg-iters", "5")
     assert len(p["pcg"]["member_iteration_ms"]) == 2 and p["pcg"]["slowest_member_iteration_ms"] > 0
-    s = run_bench(*SMALL, "--variants", "0", "--pcg-iters", "5")
+    s = run_bench(*SMALL, "--full", "--variants", "0", "--pcg-iters", "5")
     assert s["pcg_iteration"]["iteration_ms"] > s["roofline"]["kernel_ms_avg"]  # (as in the single-GPU line)
 
 

@@ -23,7 +23,7 @@ def _free_port():
 @pytest.mark.parametrize("workload", ["c2", "c4"])
 def test_bench_rank_branch_one_rank(workload):
     args = ["--gpus", "1", "--rank-path", "1", "--workload", workload, "--steps", "5", "--warmup", "2",
-            "--no-cpu-baseline", "--deadline", "240"]
+            "--full", "--no-cpu-baseline", "--deadline", "240"]
     if workload == "c2":
         args += ["--c2-n", "24"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
