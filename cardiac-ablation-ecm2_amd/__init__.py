@@ -797,7 +797,24 @@ _PAR_SIGS = {
                                      ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int,
                                      ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                      ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]),
+    "ecm2_ode_step_source": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                            ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                            ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                            ctypes.c_void_p]),
     "ecm2_operator_destroy": (None, [ctypes.c_void_p]),
+    "ecm2_linear_form_default_q1d": (ctypes.c_int, [ctypes.c_int]),
+    "ecm2_linear_form_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                               ctypes.POINTER(ctypes.c_void_p)]),
+    "ecm2_linear_form_set_element_nodes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "ecm2_linear_form_set_jacobians": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "ecm2_linear_form_set_attributes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "ecm2_linear_form_add_domain_integrator": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                              ctypes.c_int]),
+    "ecm2_linear_form_assemble": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "ecm2_linear_form_info": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_int)] * 5),
+    "ecm2_linear_form_destroy": (None, [ctypes.c_void_p]),
 }
 
 
@@ -1138,13 +1155,133 @@ def ode_implicit_coeff(ode_type: int) -> float:
 
 
 def ode_step(ode_type: int, T: Operator, K: Operator, dt: float, u, ess=None, rel_tol=1e-10, max_iter=500,
-             jacobi=True, stream=None):
+             jacobi=True, stream=None, source=None):
     """One implicit step of M du/dt = -K u (ex16 ConductionOperator, slope form) on device vector u
     (in place).  T must be M + c dt K with c = ode_implicit_coeff(ode_type).
+    source: a device true-dof vector b in the operators' numbering (e.g. LinearForm.Assemble's),
+    frozen over the step: M du/dt = -K u + b (ecm2_ode_step_source).
     Returns (stage solves, total PCG iterations, converged)."""
     ns, it, conv = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     n_ess = 0 if ess is None else int(ess.numel())
-    _check(_par_lib().ecm2_ode_step(ode_type, T._h, K._h, dt, _dev_ptr(u), _dev_ptr(ess) if n_ess else None, n_ess,
-                                    rel_tol, max_iter, 1 if jacobi else 0, ctypes.byref(ns), ctypes.byref(it),
-                                    ctypes.byref(conv), _stream(stream)))
+    if source is None:
+        _check(_par_lib().ecm2_ode_step(ode_type, T._h, K._h, dt, _dev_ptr(u), _dev_ptr(ess) if n_ess else None,
+                                        n_ess, rel_tol, max_iter, 1 if jacobi else 0, ctypes.byref(ns),
+                                        ctypes.byref(it), ctypes.byref(conv), _stream(stream)))
+        return ns.value, it.value, bool(conv.value)
+    _check_field(_OdeSource(), source, T.size)
+    _check(_par_lib().ecm2_ode_step_source(ode_type, T._h, K._h, _dev_ptr(source), dt, _dev_ptr(u),
+                                           _dev_ptr(ess) if n_ess else None, n_ess, rel_tol, max_iter,
+                                           1 if jacobi else 0, ctypes.byref(ns), ctypes.byref(it), ctypes.byref(conv),
+                                           _stream(stream)))
     return ns.value, it.value, bool(conv.value)
+
+
+class _OdeSource:
+    """(names ode_step's source in _check_field's messages)"""
+
+
+# ----------------------------------------------------------------------------
+# Linear form (LinearForm + DomainLFIntegrator on the device path)
+# ----------------------------------------------------------------------------
+COEFF_JOULE = 11
+
+
+class JouleHeatingCoefficient:
+    """The RF Joule heat sigma(T) |grad phi|^2 of a potential phi (CUDA L-vector on the linear form's
+    own space): sigma = sigma (1 + slope (T - t_ref)) with T another CUDA L-vector, or the constant
+    sigma when T is None (JouleHeatingCoefficient::Eval, joule_solver.cpp:898; the gradient as
+    GradientGridFunctionCoefficient).  A linear form's source only."""
+
+    def __init__(self, phi, sigma=1.0, slope=0.0, t_ref=0.0, T=None):
+        self.phi, self.T = phi, T
+        self.sigma, self.slope, self.t_ref = float(sigma), float(slope), float(t_ref)
+
+
+class DomainLFIntegrator:
+    """DomainLFIntegrator(Q) (lininteg.hpp:116): (f, v) for a scalar source -- ConstantCoefficient,
+    QuadratureCoefficient, GridFunctionCoefficient, AffineGridFunctionCoefficient or
+    JouleHeatingCoefficient."""
+
+    def __init__(self, coeff):
+        self.coeff = coeff
+
+
+def linear_form_default_q1d(order: int) -> int:
+    """Points per direction of DomainLFIntegrator's default rule (order 2 p: p + 1)."""
+    return _par_lib().ecm2_linear_form_default_q1d(order)
+
+
+class LinearForm:
+    """LinearForm on the device path (LinearFormExtension::Assemble, linearform_ext.cpp:20-68):
+    b = sum of its DomainLFIntegrators, each evaluated by one fused HIP kernel and summed by the
+    CSR transpose (deterministic).  geometry: "nodes" (the mesh's trilinear corners) or "jacobians"
+    (SetJacobians before Assemble).  q1d = 0: the integrator's default rule, p + 1 points."""
+
+    def __init__(self, fes: H1Space, q1d: int = 0, geometry: str = "nodes"):
+        if geometry not in ("nodes", "jacobians"):
+            raise ECM2Error(f"unknown geometry {geometry!r}")
+        lib = _par_lib()
+        self.fes = fes
+        self._keep = []
+        self._marked = False
+        gm = fes.gather_map()
+        h = ctypes.c_void_p()
+        _check(lib.ecm2_linear_form_create(fes.ne, fes.order, fes.ndofs, _np_ptr(gm), q1d, ctypes.byref(h)))
+        self._h = h
+        if geometry == "nodes":
+            en = fes.mesh.element_nodes()
+            _check(lib.ecm2_linear_form_set_element_nodes(h, _np_ptr(en)))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.ecm2_linear_form_destroy(self._h)
+            self._h = None
+
+    def SetJacobians(self, J):
+        """GeometricFactors::JACOBIANS at the form's rule (NQ x 3 x 3 x NE, torch CUDA float64)."""
+        info = self.info()
+        _check_points(self, J, ((),), None, None, flat_ok=True)
+        if J.numel() != 9 * info["ne"] * info["q1d"] ** 3:
+            raise ECM2Error(f"LinearForm: {J.numel()} Jacobian entries, expected {info['q1d'] ** 3} x 3 x 3 x {info['ne']}")
+        self._keep.append(J)
+        _check(_lib.ecm2_linear_form_set_jacobians(self._h, _dev_ptr(J)))
+
+    def AddDomainIntegrator(self, integ, elem_marker=None):
+        """LinearForm::AddDomainIntegrator(lfi[, elem_marker]): with a marker (0 / 1 per attribute) the
+        integrator acts on the elements whose attribute a has elem_marker[a - 1]."""
+        info = self.info()
+        c = integ.coeff
+        data2 = None
+        if isinstance(c, JouleHeatingCoefficient):
+            _check_field(c, c.phi, info["ndofs"])
+            if c.T is not None:
+                _check_field(c, c.T, info["ndofs"])
+                data2 = _dev_ptr(c.T)
+            params = (ctypes.c_double * 3)(c.sigma, c.slope, c.t_ref)
+            self._keep += [c.phi, c.T, params]
+            kind, data, params = COEFF_JOULE, _dev_ptr(c.phi), ctypes.cast(params, ctypes.c_void_p)
+        elif isinstance(c, (ConstantCoefficient, QuadratureCoefficient, GridFunctionCoefficient,
+                            AffineGridFunctionCoefficient)):
+            kind, data, params = _integrator_args(c, self._keep, info["ne"], info["q1d"] ** 3, info["ndofs"])
+        else:
+            raise ECM2Error(f"{type(c).__name__} is not a scalar source of a DomainLFIntegrator")
+        mk, n = None, 0
+        if elem_marker is not None:
+            mk = np.ascontiguousarray(elem_marker, np.int32)
+            n = mk.size
+            self._marked = True
+        _check(_lib.ecm2_linear_form_add_domain_integrator(self._h, kind, data, data2, params,
+                                                           _np_ptr(mk) if mk is not None else None, n))
+
+    def Assemble(self, b, stream=None):
+        """b (CUDA float64 [ndofs]) = the form's vector; the coefficients' tensors are read now."""
+        _check_field(self, b, self.fes.ndofs)
+        if self._marked:  # the mesh's current attributes, as the reference reads them
+            attr = np.ascontiguousarray(self.fes.mesh.GetAttributes())
+            _check(_lib.ecm2_linear_form_set_attributes(self._h, _np_ptr(attr)))
+        _check(_lib.ecm2_linear_form_assemble(self._h, _dev_ptr(b), _stream(stream)))
+
+    def info(self) -> dict:
+        v = [ctypes.c_int() for _ in range(5)]
+        _check(_lib.ecm2_linear_form_info(self._h, *[ctypes.byref(a) for a in v]))
+        return dict(zip(["ne", "ndofs", "d1d", "q1d", "n_integrators"], [a.value for a in v]))

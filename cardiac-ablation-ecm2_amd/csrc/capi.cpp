@@ -5,6 +5,7 @@
 #include "fe.hpp"
 #include "mesh.hpp"
 #include "pa_form.hpp"
+#include "linear_form.hpp"
 #include "bricks.hpp"
 #include "par_form.hpp"
 #include "partition.hpp"
@@ -37,6 +38,10 @@ struct ecm2_par_form
 struct ecm2_operator
 {
    std::unique_ptr<ecm2::LinOp> op;
+};
+struct ecm2_linear_form
+{
+   ecm2::LinearForm f;
 };
 
 namespace
@@ -101,7 +106,12 @@ ecm2::CoeffDesc make_coeff(int coeff_kind, const double *data, const double *par
       NEED(data);
       for (int i = 0; i < c.dim(); i++) { c.cv[i] = data[i]; }
    }
-   else { ECM2_VERIFY(false, ecm2::ERR_ARG, "unknown coefficient kind " << coeff_kind); }
+   else
+   {
+      ECM2_VERIFY(coeff_kind != ECM2_COEFF_JOULE, ecm2::ERR_ARG,
+                  "ECM2_COEFF_JOULE is a linear-form source, not a bilinear form's coefficient");
+      ECM2_VERIFY(false, ecm2::ERR_ARG, "unknown coefficient kind " << coeff_kind);
+   }
    // (a null grid function is refused by PAForm::add_integrator unless the form has no dofs: a rank
    // with an empty local space passes an empty tensor's null data pointer)
    return c;
@@ -963,22 +973,113 @@ double ecm2_ode_implicit_coeff(int type)
    catch (...) { return 0.0; }
 }
 
-int ecm2_ode_step(int type, ecm2_operator *T, ecm2_operator *K, double dt, double *u, const int *ess,
-                  int n_ess, double rel_tol, int max_iter, int jacobi, int *solves, int *iterations,
-                  int *converged, void *stream)
+int ecm2_ode_step_source(int type, ecm2_operator *T, ecm2_operator *K, const double *b, double dt, double *u,
+                         const int *ess, int n_ess, double rel_tol, int max_iter, int jacobi, int *solves,
+                         int *iterations, int *converged, void *stream)
 {
    return guard([&] {
       NEED(T); NEED(K); NEED(u);
       ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
       const ecm2::StepStats st = ecm2::ode_step(type, *T->op, *K->op, dt, u, ess, n_ess, rel_tol, max_iter,
-                                                jacobi != 0, S(stream));
+                                                jacobi != 0, S(stream), b);
       if (solves) { *solves = st.solves; }
       if (converged) { *converged = st.converged ? 1 : 0; }
       if (iterations) { *iterations = st.iterations; }
    });
 }
 
+int ecm2_ode_step(int type, ecm2_operator *T, ecm2_operator *K, double dt, double *u, const int *ess,
+                  int n_ess, double rel_tol, int max_iter, int jacobi, int *solves, int *iterations,
+                  int *converged, void *stream)
+{
+   return ecm2_ode_step_source(type, T, K, nullptr, dt, u, ess, n_ess, rel_tol, max_iter, jacobi, solves, iterations,
+                               converged, stream);
+}
+
 void ecm2_operator_destroy(ecm2_operator *op) { delete op; }
+
+// ---- linear form ----
+int ecm2_linear_form_default_q1d(int order) { return ecm2::LinearForm::default_q1d(order); }
+
+int ecm2_linear_form_create(int ne, int order, int ndofs, const int *gather_map, int q1d, ecm2_linear_form **out)
+{
+   return guard([&] {
+      NEED(out);
+      *out = nullptr;
+      *out = new ecm2_linear_form{ecm2::LinearForm(ne, order, ndofs, gather_map, q1d)};
+   });
+}
+
+int ecm2_linear_form_set_element_nodes(ecm2_linear_form *lf, const double *enodes)
+{
+   return guard([&] { NEED(lf); lf->f.set_element_nodes(enodes); });
+}
+
+int ecm2_linear_form_set_jacobians(ecm2_linear_form *lf, const double *J)
+{
+   return guard([&] { NEED(lf); lf->f.set_jacobians(J); });
+}
+
+int ecm2_linear_form_set_attributes(ecm2_linear_form *lf, const int *attr)
+{
+   return guard([&] { NEED(lf); lf->f.set_attributes(attr); });
+}
+
+int ecm2_linear_form_add_domain_integrator(ecm2_linear_form *lf, int coeff_kind, const double *data,
+                                           const double *data2, const double *params, const int *marker,
+                                           int n_marker)
+{
+   return guard([&] {
+      NEED(lf);
+      ecm2::SourceDesc c;
+      c.kind = coeff_kind;
+      if (coeff_kind == ECM2_COEFF_CONSTANT)
+      {
+         NEED(data);
+         c.value = data[0];
+      }
+      else if (coeff_kind == ECM2_COEFF_QUAD) { c.quad = data; }
+      else if (coeff_kind == ECM2_COEFF_GRIDFUNC) { c.lvec = data; }
+      else if (coeff_kind == ECM2_COEFF_GRIDFUNC_AFFINE || coeff_kind == ECM2_COEFF_JOULE)
+      {
+         NEED(params);
+         c.lvec = data;
+         c.scale = params[0];
+         c.slope = params[1];
+         c.t_ref = params[2];
+         if (coeff_kind == ECM2_COEFF_JOULE) { c.lvec2 = data2; }
+      }
+      else
+      {
+         ECM2_VERIFY(coeff_kind >= ECM2_COEFF_CONSTANT && coeff_kind <= ECM2_COEFF_JOULE, ecm2::ERR_ARG,
+                     "unknown coefficient kind " << coeff_kind);
+         ECM2_VERIFY(false, ecm2::ERR_ARG, "coefficient kind " << coeff_kind
+                                                                << " is not a scalar source of a DomainLFIntegrator");
+      }
+      ECM2_VERIFY(coeff_kind == ECM2_COEFF_JOULE || data2 == nullptr, ecm2::ERR_ARG,
+                  "data2 belongs to ECM2_COEFF_JOULE alone");
+      lf->f.add_domain_integrator(c, marker, n_marker);
+   });
+}
+
+int ecm2_linear_form_assemble(ecm2_linear_form *lf, double *b, void *stream)
+{
+   return guard([&] { NEED(lf); lf->f.assemble(b, S(stream)); });
+}
+
+int ecm2_linear_form_info(const ecm2_linear_form *lf, int *ne, int *ndofs, int *d1d, int *q1d, int *n_integrators)
+{
+   return guard([&] {
+      NEED(lf);
+      if (ne) { *ne = lf->f.ne(); }
+      if (ndofs) { *ndofs = lf->f.ndofs(); }
+      if (d1d) { *d1d = lf->f.d1d(); }
+      if (q1d) { *q1d = lf->f.q1d(); }
+      if (n_integrators) { *n_integrators = lf->f.n_integrators(); }
+   });
+}
+
+void ecm2_linear_form_destroy(ecm2_linear_form *lf) { delete lf; }
 
 int ecm2_par_form_timing(ecm2_par_form *f, int enable)
 {

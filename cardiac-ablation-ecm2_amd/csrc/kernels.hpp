@@ -1,7 +1,7 @@
 // kernels.hpp -- host launchers for the gfx950 HIP kernels (k_setup.hip: qdata and
 // coefficient setup; k_tpe.hip: thread-per-element p <= 2 apply and diagonal; k_line.hip:
 // line / brick p >= 3 apply and the sum-factorised diagonal; k_misc.hip: workgroup-per-element
-// apply, restriction, vector and solver kernels).
+// apply, restriction, vector and solver kernels; k_lform.hip: the linear form's element vectors).
 //
 // Quadrature-data layouts (the qdata a PA form owns):
 //  * BLOCKED (fused thread-per-element kernel): elements in blocks of 64 (one
@@ -131,7 +131,10 @@ struct QLayout
 enum CoeffKind : int { COEFF_CONSTANT = 0, COEFF_QUAD = 1, COEFF_GRIDFUNC_AFFINE = 2, COEFF_GRIDFUNC_PERFUSION = 3,
                        COEFF_QUAD_VECTOR = 4, COEFF_QUAD_SYMMATRIX = 5, COEFF_QUAD_MATRIX = 6,
                        COEFF_CONST_VECTOR = 7, COEFF_CONST_SYMMATRIX = 8, COEFF_CONST_MATRIX = 9,
-                       COEFF_GRIDFUNC = 10 };
+                       COEFF_GRIDFUNC = 10,
+                       // linear forms only: the RF Joule heat sigma(T) |grad phi|^2 of a potential phi on the
+                       // form's space (LFormArgs below; JouleHeatingCoefficient::Eval, joule_solver.cpp:898)
+                       COEFF_JOULE = 11 };
 struct CoeffDesc
 {
    int kind = COEFF_CONSTANT;
@@ -473,6 +476,30 @@ int brick_points(int D, int bz);
 // gather map; output by atomics into a zeroed y) or E-vectors (accumulated).
 void apply_wpe(int D, int Q, bool mass, bool diff, const ApplyArgs &a, bool in_evec,
                bool out_evec, const Basis1D &b, hipStream_t s);
+
+// ---- linear form (k_lform.hip) ----
+// One DomainLFIntegrator's element vectors be[e][nd] = B^T B^T B^T (W_q f_q det J_q) (DLFEvalAssemble3D,
+// lininteg_domain_kernels.hpp:164-300), f_q evaluated in the kernel.  kind: COEFF_CONSTANT (value),
+// COEFF_QUAD (quad [ne][nq]), COEFF_GRIDFUNC / _GRIDFUNC_AFFINE (lvec, the law's scale, slope, t_ref),
+// COEFF_JOULE (lvec = phi, lvec2 = T or null, sigma = scale (1 + slope (T_q - t_ref))).  Geometry: enodes
+// (device [ne][3][8] lexicographic corners) or J (device, MFEM layout NQ x 3 x 3 x NE), exactly one.
+// emark (device [ne], or null: all): an element with emark[e] == 0 writes zeros.
+struct LFormArgs
+{
+   int ne = 0, kind = COEFF_CONSTANT;
+   const int *gmap = nullptr;       // native [e][nd]
+   const double *enodes = nullptr, *J = nullptr;
+   const double *W = nullptr;       // device tensor weights [nq]
+   QPts qp = {};                    // 1D Gauss-Legendre points (corner geometry)
+   double value = 0.0;
+   const double *quad = nullptr, *lvec = nullptr, *lvec2 = nullptr;
+   double scale = 1.0, slope = 0.0, t_ref = 0.0;
+   const int *emark = nullptr;
+   double *be = nullptr;            // device [ne][nd], overwritten
+};
+// (D1D, Q1D) instantiated: p = 1..4 with Q1D = p + 1 or p + 2
+bool has_lform(int D, int Q);
+void lform_element_vectors(int D, int Q, const LFormArgs &a, const Basis1D &b, hipStream_t s);
 
 // ---- ElementRestriction ----
 void restriction_mult(long n, int nd, const int *gmap_native, const double *x, double *xe,

@@ -1356,21 +1356,28 @@ size_t PAForm::algorithmic_bytes() const
    return 8ull * ne_ * NQ_ * nc + 16ull * n_owned_ + 4ull * ne_ * ND_;
 }
 
-void PAForm::ensure_csr()
+void build_restriction_csr(const std::vector<int> &gmap, int ndofs, std::vector<int> &off, std::vector<int> &idx)
 {
-   if (csr_off_.size() || ndofs_ == 0) { return; }
    // ElementRestriction ctor CSR build (restriction.cpp:68-106).
-   std::vector<int> off(ndofs_ + 1, 0), idx((size_t)ne_ * ND_);
-   for (int g : gmap_host_) { off[(g >= 0 ? g : -1 - g) + 1]++; }
-   for (int i = 1; i <= ndofs_; i++) { off[i] += off[i - 1]; }
-   for (size_t lid = 0; lid < gmap_host_.size(); lid++)
+   off.assign(ndofs + 1, 0);
+   idx.resize(gmap.size());
+   for (int g : gmap) { off[(g >= 0 ? g : -1 - g) + 1]++; }
+   for (int i = 1; i <= ndofs; i++) { off[i] += off[i - 1]; }
+   for (size_t lid = 0; lid < gmap.size(); lid++)
    {
-      const int g = gmap_host_[lid];
+      const int g = gmap[lid];
       const int d = g >= 0 ? g : -1 - g;
       idx[off[d]++] = g >= 0 ? (int)lid : (int)(-1 - (long)lid);
    }
-   for (int i = ndofs_; i > 0; i--) { off[i] = off[i - 1]; }
+   for (int i = ndofs; i > 0; i--) { off[i] = off[i - 1]; }
    off[0] = 0;
+}
+
+void PAForm::ensure_csr()
+{
+   if (csr_off_.size() || ndofs_ == 0) { return; }
+   std::vector<int> off, idx;
+   build_restriction_csr(gmap_host_, ndofs_, off, idx);
    csr_off_.upload(off);
    csr_idx_.upload(idx);
    ECM2_HIP(hipDeviceSynchronize());

@@ -43,6 +43,11 @@ enum ScatterMode : int
 
 enum IntegratorKind : int { INTEG_MASS = 0, INTEG_DIFFUSION = 1 };
 
+// The CSR transpose of a gather map [ne][nd] (ElementRestriction's offsets / indices,
+// restriction.cpp:68-106; index -1 - lid = minus sign) that kern::restriction_mult_transpose sums:
+// shared by PAForm and LinearForm.
+void build_restriction_csr(const std::vector<int> &gmap, int ndofs, std::vector<int> &off, std::vector<int> &idx);
+
 class PAForm
 {
 public:

@@ -359,17 +359,18 @@ double ode_implicit_coeff(int type)
 }
 
 StepStats ode_step(int type, LinOp &T, LinOp &K, double dt, double *u, const int *ess, int n_ess,
-                   double rel_tol, int max_iter, bool jacobi, hipStream_t s)
+                   double rel_tol, int max_iter, bool jacobi, hipStream_t s, const double *b)
 {
    ECM2_VERIFY(ode_implicit_supported(type), ERR_ARG, "unsupported implicit ODE solver type " << type);
    ECM2_VERIFY(T.size() == K.size(), ERR_ARG, "T and K sizes differ");
    const int n = T.size();
    StepStats st;
    DeviceArray<double> k(std::max(n, 1)), y(std::max(n, 1)), z(std::max(n, 1)), rhs(std::max(n, 1));
-   // ConductionOperator::ImplicitSolve (ex16.cpp:327-354), slope form: T k = -K u_stage
+   // ConductionOperator::ImplicitSolve (ex16.cpp:327-354), slope form: T k = -K u_stage [+ b]
    auto implicit_solve = [&](const double *us, double *kk) {
       K.mult(us, rhs.data(), s);
       kern::scale(n, -1.0, rhs.data(), s);
+      if (b) { kern::add_scaled(n, rhs.data(), 1.0, b, rhs.data(), s); }
       if (n_ess) { kern::set_values(n_ess, ess, 0.0, rhs.data(), s); }
       const PCGResult r = pcg_solve(T, ess, n_ess, rhs.data(), kk, rel_tol, 0.0, max_iter, jacobi, s);
       st.solves++;

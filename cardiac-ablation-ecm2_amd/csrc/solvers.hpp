@@ -142,7 +142,10 @@ struct StepStats
 // One implicit step u <- u(t + dt) of M du/dt = -K u (ex16 ConductionOperator, slope
 // form): each stage solves T k = -K u_stage with T = M + c*dt*K supplied assembled by
 // the caller (c = ode_implicit_coeff(type)); ess dofs keep their values (k = 0 there).
+// b (optional, device, true dofs in the operator's numbering): a source frozen over the step,
+// M du/dt = -K u + b -- every stage solves T k = -K u_stage + b (essential rows zeroed as before);
+// null: exactly the homogeneous step.
 StepStats ode_step(int type, LinOp &T, LinOp &K, double dt, double *u, const int *ess_dev, int n_ess,
-                   double rel_tol, int max_iter, bool jacobi, hipStream_t s);
+                   double rel_tol, int max_iter, bool jacobi, hipStream_t s, const double *b = nullptr);
 
 } // namespace ecm2

@@ -360,7 +360,62 @@ double ecm2_ode_implicit_coeff(int type);
 int ecm2_ode_step(int type, ecm2_operator *T, ecm2_operator *K, double dt, double *u, const int *ess,
                   int n_ess, double rel_tol, int max_iter, int jacobi, int *solves, int *iterations,
                   int *converged, void *stream);
+/* ecm2_ode_step with a source: one step of M du/dt = -K u + b, b a device true-dof vector in the
+ * operator's own numbering (serial form, RCCL rank or loopback group alike), frozen over the step
+ * (a TimeDependentOperator whose ImplicitSolve adds a LinearForm's vector to the right-hand side,
+ * as the Joule miniapp's heat solve adds its DomainLFIntegrator(Wcoeff) form, joule_solver.cpp:
+ * 401-, 616): every stage solves
+ * T k = -K u_stage + b with the essential rows zeroed.  b == NULL is exactly ecm2_ode_step. */
+int ecm2_ode_step_source(int type, ecm2_operator *T, ecm2_operator *K, const double *b, double dt, double *u,
+                         const int *ess, int n_ess, double rel_tol, int max_iter, int jacobi, int *solves,
+                         int *iterations, int *converged, void *stream);
 void ecm2_operator_destroy(ecm2_operator *op);
+
+/* ------------------------------------------------------------------------ */
+/* The device linear form: LinearForm + DomainLFIntegrator on the device path */
+/* (LinearFormExtension::Assemble, fem/linearform_ext.cpp:20-68)              */
+/* ------------------------------------------------------------------------ */
+typedef struct ecm2_linear_form ecm2_linear_form;
+/* Linear forms only: the RF Joule heat of a potential phi on the form's space,
+ *   f = sigma0 (1 + slope (T - t_ref)) |grad phi|^2
+ * (GradientGridFunctionCoefficient into InnerProductCoefficient, fem/coefficient.hpp:872, :1760;
+ * JouleHeatingCoefficient::Eval, miniapps/electromagnetics/joule_solver.cpp:898): data = phi's device
+ * L-vector, params[0..2] = (sigma0, slope, t_ref), data2 = T's device L-vector or NULL (sigma = sigma0).
+ * A bilinear form refuses it (ECM2_ERR_ARG). */
+#define ECM2_COEFF_JOULE 11
+/* Host only: DomainLFIntegrator(Q, a = 2, b = 0) integrates with the rule of order a p + b = 2 p
+ * (lininteg.hpp:116), i.e. p + 1 Gauss-Legendre points per direction (intrules.cpp:1181-1200). */
+int ecm2_linear_form_default_q1d(int order);
+/* LinearForm(fes) + LinearFormExtension (linearform.hpp, linearform_ext.cpp:18): gather_map as
+ * ecm2_pa_form_create; q1d <= 0 selects the default above.  Kernels exist for order 1..4 with
+ * q1d = order + 1 or order + 2 (DomainLFIntegrator's specialisations, lininteg_domain.cpp:104-115,
+ * plus the forms' order 1, q1d 3 rule): anything else is ECM2_ERR_UNSUPPORTED. */
+int ecm2_linear_form_create(int ne, int order, int ndofs, const int *gather_map, int q1d, ecm2_linear_form **out);
+/* Geometry, as ecm2_pa_form_set_element_nodes / _set_jacobians (the last call wins; the Jacobians
+ * must stay valid for as long as the form is assembled): GeometricFactors DETERMINANTS / JACOBIANS
+ * (lininteg_domain.cpp:38-41) are evaluated in the kernel, never stored. */
+int ecm2_linear_form_set_element_nodes(ecm2_linear_form *lf, const double *enodes /* host [ne][3][8] */);
+int ecm2_linear_form_set_jacobians(ecm2_linear_form *lf, const double *J /* device, NQ x 3 x 3 x NE */);
+/* Element attributes for marked integrators (Mesh::GetAttribute), host [ne]. */
+int ecm2_linear_form_set_attributes(ecm2_linear_form *lf, const int *attr /* host [ne] */);
+/* LinearForm::AddDomainIntegrator(new DomainLFIntegrator(Q)[, elem_marker]) (linearform.hpp).
+ * coeff_kind: ECM2_COEFF_CONSTANT (data[0], host), _QUAD (device [ne][nq]), _GRIDFUNC (device
+ * L-vector), _GRIDFUNC_AFFINE (device L-vector, params = scale, slope, t_ref) or _JOULE (above);
+ * data2 is NULL except for _JOULE.  Vector and matrix kinds (and _GRIDFUNC_PERFUSION) are
+ * ECM2_ERR_ARG.  marker: host [n_marker], 0 / 1 per attribute (an excluded element contributes
+ * zeros, DLFEvalAssemble3D's markers[e] == 0), NULL: all elements.  Device pointers must stay valid
+ * for as long as the form is assembled: every assemble re-reads them. */
+int ecm2_linear_form_add_domain_integrator(ecm2_linear_form *lf, int coeff_kind, const double *data,
+                                           const double *data2, const double *params, const int *marker,
+                                           int n_marker);
+/* LinearForm::Assemble -> LinearFormExtension::Assemble (linearform_ext.cpp:20-68): b = the sum of
+ * the integrators in the order they were added (the first's R^T stores, the later ones add,
+ * :64-67).  No atomics: two calls on the same inputs give bitwise equal vectors. */
+int ecm2_linear_form_assemble(ecm2_linear_form *lf, double *b /* device [ndofs], overwritten */, void *stream);
+/* Introspection (any output may be NULL). */
+int ecm2_linear_form_info(const ecm2_linear_form *lf, int *ne, int *ndofs, int *d1d, int *q1d, int *n_integrators);
+/* ~LinearForm. */
+void ecm2_linear_form_destroy(ecm2_linear_form *lf);
 
 /* ------------------------------------------------------------------------ */
 /* Distributed form: ParBilinearForm / RAPOperator(P, A, P) over RCCL          */
