@@ -1,18 +1,15 @@
-// pa_form.cpp -- see pa_form.hpp.
+// pa_form.cpp -- see pa_form.hpp.  The device side of a form: geometry, qdata, uploads and kernel
+// launches.  What the fused kernels' deterministic scatter needs (element order, merge flags, maps,
+// lattice units, partial slots, the summation plan) is planned on the host in scatter_plan.cpp;
+// plan_tpe / plan_line below call it and upload the result.
 #include "pa_form.hpp"
-#include "bricks.hpp"
+#include "scatter_plan.hpp"
 
 #include <algorithm>
-#include <climits>
-#include <map>
-#include <tuple>
-#include <array>
 #include <cmath>
 #include <cstdlib>
-#include <cstdio>
 #include <cstring>
 #include <string>
-#include <unordered_map>
 
 namespace ecm2
 {
@@ -192,466 +189,6 @@ void PAForm::set_element_order(const int *perm)
    assembled_ = false;
 }
 
-namespace
-{
-// In-wave face assembly plan for the blocked (64 elements per wave) layout.
-// Directions x, y, z pair lane l with l+1, l+4, l+16: lane l adds the partner's
-// low face (index 0 along the direction) into its high face (index D-1) when all
-// face dofs coincide and no nonzero value could land in an entry that no longer
-// holds its dof; the partner then zeroes that face.  After the three passes the
-// "holding" entries (holds[(b*64+l)*ND+a]) carry each dof's in-wave sum, and
-// hcount[d] counts the holders of dof d in the whole mesh: a dof held once is
-// plain-stored, otherwise it is "shared" (partial slot or atomic add).
-// In-wave face assembly plan of the blocked layout (see tpe_assemble_store): per 64-lane
-// block and direction, lane l receives lane l + off's low face into its high face when the
-// faces coincide; then (xwave) across the waves of a workgroup group: a wave whose 16
-// high-face lanes all coincide with another wave's 16 low-face lanes receives those through
-// LDS.  groups: [first block, end block, link allowed] of every workgroup (<= 4 blocks, in
-// the launch's grouping: from each apply segment's first block).  Lane flags: bits 1|4|16 receive x|y|z in-wave, 2|8|32 low face
-// sent (in-wave or across waves), 64|128|256 receive x|y|z across waves, bits 9-11 | 12-14 |
-// 15-17 the sending wave (within the group) for x | y | z.
-void build_merge_plan(int ne, int D, const std::vector<int> &gmap_int, int ndofs,
-                      std::vector<char> &holds, std::vector<int> &hcount, std::vector<int> &flags,
-                      const std::vector<std::array<int, 3>> &groups)
-{
-   const int ND = D * D * D, nblk = (ne + 63) / 64;
-   flags.assign((size_t)nblk * 64, 0);
-   holds.assign((size_t)nblk * 64 * ND, 0);
-   hcount.assign(ndofs, 0);
-   auto dofv = [](int g) { return g >= 0 ? g : -1 - g; };
-   auto face = [D](int dir, int s, int i, int j) {
-      if (dir == 0) { return (j * D + i) * D + s; }
-      if (dir == 1) { return (j * D + s) * D + i; }
-      return (s * D + j) * D + i;
-   };
-   const int off[3] = {1, 4, 16}, recv[3] = {1, 4, 16}, sent[3] = {2, 8, 32};
-   auto act = [&](int b, int l) { return b * 64 + l < ne; };
-   auto dof = [&](int b, int l, int a) { return dofv(gmap_int[((size_t)b * 64 + l) * ND + a]); };
-   auto H = [&](int b, int l, int a) -> char & { return holds[((size_t)b * 64 + l) * ND + a]; };
-   auto F = [&](int b, int l) -> int & { return flags[(size_t)b * 64 + l]; };
-   for (int b = 0; b < nblk; b++)
-      for (int l = 0; l < 64; l++)
-         for (int a = 0; a < ND; a++) { H(b, l, a) = act(b, l); }
-   for (const auto &grp : groups)
-   {
-      const int g0 = grp[0], g1 = grp[1];
-      const bool xw = grp[2] != 0;
-      for (int dir = 0; dir < 3; dir++)
-      {
-         for (int b = g0; b < g1; b++)
-         {
-            for (int l = 0; l + off[dir] < 64; l++)
-            {
-               const int m = l + off[dir];
-               if (!act(b, l) || !act(b, m)) { continue; }
-               bool ok = true;
-               for (int j = 0; j < D && ok; j++)
-                  for (int i = 0; i < D && ok; i++)
-                  {
-                     const int ar = face(dir, D - 1, i, j), as = face(dir, 0, i, j);
-                     ok = dof(b, l, ar) == dof(b, m, as) && (H(b, l, ar) || !H(b, m, as));
-                  }
-               if (!ok) { continue; }
-               F(b, l) |= recv[dir];
-               F(b, m) |= sent[dir];
-            }
-            for (int m = 0; m < 64; m++)
-            {
-               if (!(F(b, m) & sent[dir])) { continue; }
-               for (int j = 0; j < D; j++)
-                  for (int i = 0; i < D; i++) { H(b, m, face(dir, 0, i, j)) = 0; }
-            }
-         }
-         if (!xw) { continue; }
-         // across the group's waves: wave br's 16 high-face lanes <- wave bs's low-face lanes
-         for (int br = g0; br < g1; br++)
-         {
-            for (int bs = g0; bs < g1; bs++)
-            {
-               if (bs == br) { continue; }
-               bool ok = true;
-               for (int l = 0; l < 64 && ok; l++)
-               {
-                  if ((l / off[dir]) % 4 != 3) { continue; }
-                  const int m = l - 3 * off[dir];
-                  ok = act(br, l) && act(bs, m) && !(F(bs, m) & sent[dir]);
-                  for (int j = 0; j < D && ok; j++)
-                     for (int i = 0; i < D && ok; i++)
-                     {
-                        const int ar = face(dir, D - 1, i, j), as = face(dir, 0, i, j);
-                        ok = dof(br, l, ar) == dof(bs, m, as) && H(br, l, ar) && H(bs, m, as);
-                     }
-               }
-               if (!ok) { continue; }
-               for (int l = 0; l < 64; l++)
-               {
-                  if ((l / off[dir]) % 4 != 3) { continue; }
-                  const int m = l - 3 * off[dir];
-                  F(br, l) |= (64 << dir) | ((bs - g0) << (9 + 3 * dir));
-                  F(bs, m) |= sent[dir];
-                  for (int j = 0; j < D; j++)
-                     for (int i = 0; i < D; i++) { H(bs, m, face(dir, 0, i, j)) = 0; }
-               }
-               break;  // one sender per receiving wave and direction
-            }
-         }
-      }
-   }
-   for (int b = 0; b < nblk; b++)
-      for (int l = 0; l < 64; l++)
-         for (int a = 0; a < ND; a++) { if (H(b, l, a)) { hcount[dof(b, l, a)]++; } }
-}
-} // namespace
-
-// Second-pass plan of the deterministic scatter: every dof not held exactly once with its
-// partial slots in ascending order; dofs held by nobody get an empty list (y = 0).  The
-// owned dofs come first, then the ghosts (split form); within each range the list is
-// ordered by first slot, so neighbouring threads of k_sum_partials read neighbouring slots.
-void PAForm::build_shared_plan(const std::vector<int> &hcount, const std::vector<int> &hdof,
-                               const std::vector<int> &hslot, hipStream_t s)
-{
-   std::vector<int> start(ndofs_ + 1, 0);
-   for (int d = 0; d < ndofs_; d++) { start[d + 1] = start[d] + (hcount[d] > 1 ? hcount[d] : 0); }
-   ECM2_VERIFY((size_t)start[ndofs_] == hdof.size(), ERR_INTERNAL, "shared holder count mismatch");
-   std::vector<int> slots_by_dof(hdof.size()), fill(start.begin(), start.end() - 1);
-   for (size_t i = 0; i < hdof.size(); i++) { slots_by_dof[fill[hdof[i]]++] = hslot[i]; }
-   std::vector<int> dofs;
-   for (int d = 0; d < ndofs_; d++) { if (hcount[d] != 1) { dofs.push_back(d); } }
-   auto key = [&](int d) -> long {
-      const long first = hcount[d] > 1 ? slots_by_dof[start[d]] : -1;
-      return (d < n_owned_ ? 0 : (1l << 40)) + first;
-   };
-   std::stable_sort(dofs.begin(), dofs.end(), [&](int p, int q) { return key(p) < key(q); });
-   ECM2_VERIFY(slots_by_dof.size() < (1ull << 31), ERR_UNSUPPORTED, "too many partial slots");
-   n_sh_ = (int)dofs.size();
-   n_sh_owned_ = 0;
-   while (n_sh_owned_ < n_sh_ && dofs[n_sh_owned_] < n_owned_) { n_sh_owned_++; }
-   n_slots_ = (long)slots_by_dof.size();
-
-   // Run compression, per range ([owned | ghost]: finish_shared runs each on its own).  1D runs:
-   // consecutive entries (in the order above) with equal holder counts whose dof and every
-   // holder's slot advance by the same steps; 2D runs: 1D runs of one shape whose first entries
-   // advance by common steps again (a face interior, a 4 x 4 lane patch).  Entries are
-   // re-emitted run by run; each dof keeps its holders in ascending slot order.
-   auto cnt = [&](int d) { return hcount[d] > 1 ? start[d + 1] - start[d] : 0; };
-   auto slot = [&](int d, int h) { return slots_by_dof[start[d] + h]; };
-   // d1 == kExplicitDofs: the run's slots are affine but its dofs are not (a numbering that is not a
-   // lattice, e.g. the reference's entity numbering): the pass reads each entry's dof from the
-   // plan's entry list instead (4 coalesced bytes per entry)
-   constexpr int kExplicitDofs = INT32_MIN;
-   struct Run { int n1, n2, c, dof0, d1, d2, t1, t2, first; std::vector<int> s0; };
-   std::vector<Run> runs;
-   std::vector<int> order;  // plan entries (dofs) in run-major order
-   for (int range = 0; range < 2; range++)
-   {
-      const int r0 = range ? n_sh_owned_ : 0, r1 = range ? n_sh_ : n_sh_owned_;
-      struct R1 { int i0, n, c, d1, t1; };
-      std::vector<R1> r1s;
-      // longest run from entry i: slots affine with a common step, dofs too unless explicit
-      auto extend = [&](int i, bool explicit_dofs, int &d1, int &t1) {
-         const int c = cnt(dofs[i]);
-         int n = 1;
-         d1 = 0;
-         t1 = 0;
-         while (i + n < r1 && n < 64 && c <= 8)
-         {
-            const int dj = dofs[i + n], dp = dofs[i + n - 1];
-            if (cnt(dj) != c) { break; }
-            const int dd = dj - dp, tt = c ? slot(dj, 0) - slot(dp, 0) : 0;
-            bool ok = n == 1 || ((explicit_dofs || dd == d1) && tt == t1);
-            for (int h = 1; h < c && ok; h++) { ok = slot(dj, h) - slot(dp, h) == tt; }
-            if (!ok) { break; }
-            if (n == 1) { d1 = dd; t1 = tt; }
-            n++;
-         }
-         return n;
-      };
-      for (int i = r0; i < r1;)
-      {
-         const int c = cnt(dofs[i]);
-         int d1, t1, e1, et1;
-         int n = extend(i, false, d1, t1);
-         const int n_ex = c ? extend(i, true, e1, et1) : 0;  // explicit-dof run length
-         if (n_ex > n && (n < 4 || n_ex >= 2 * n))  // a short affine run costs more descriptor bytes per entry
-         {
-            n = n_ex;
-            d1 = kExplicitDofs;
-            t1 = et1;
-         }
-         r1s.push_back({i, n, c, d1, t1});
-         i += n;
-      }
-      // 2D: one open run per (count, length, steps) class; a 1D run joins its class's open run
-      // when its first entry continues that run's lattice, else it opens a new one.  A run whose
-      // slots continue the lattice but whose dofs do not (the reference's numbering: the 3- and
-      // 4-holder entries of a brick edge are 1D runs of one entry each) joins the last open run
-      // of its (count, length, slot step) class instead, which becomes explicit-dof if it is not
-      // yet (only while small: an explicit entry costs 4 plan bytes, a run descriptor 48)
-      std::vector<Run> out;
-      std::vector<std::vector<int>> members;  // 1D runs of each 2D run
-      std::map<std::tuple<int, int, int, int>, int> open_aff;
-      std::map<std::tuple<int, int, int>, int> open_any;
-      auto try_join = [&](int gi, const R1 &q, int d0, int k, bool convert) {
-         Run &g = out[gi];
-         if ((g.n2 + 1) * g.n1 > 64 || q.c > 8) { return false; }
-         const int tt = q.c ? slot(d0, 0) - g.s0[0] : 0;
-         bool ok = g.n2 == 1 || tt == g.n2 * g.t2;
-         for (int h = 1; h < q.c && ok; h++) { ok = slot(d0, h) - g.s0[h] == tt; }
-         if (!ok) { return false; }
-         const bool gex = g.d1 == kExplicitDofs, qex = q.d1 == kExplicitDofs;
-         const int dd = d0 - g.dof0;
-         const bool dofs_ok = !gex && !qex && q.d1 == g.d1 && (g.n2 == 1 || dd == g.n2 * g.d2);
-         if (!gex && !dofs_ok)
-         {
-            if (!convert || g.n1 * g.n2 > 12) { return false; }
-            g.d1 = kExplicitDofs;  // the run's dofs come from the entry list from now on
-            g.d2 = 0;
-         }
-         if (g.n2 == 1) { g.t2 = tt; g.d2 = g.d1 == kExplicitDofs ? 0 : dd; }
-         g.n2++;
-         members[gi].push_back(k);
-         return true;
-      };
-      for (size_t k = 0; k < r1s.size(); k++)
-      {
-         const R1 &q = r1s[k];
-         const int d0 = dofs[q.i0];
-         const auto ka = std::make_tuple(q.c, q.n, q.d1, q.t1);
-         const auto kb = std::make_tuple(q.c, q.n, q.t1);
-         int gi = -1;
-         auto ia = open_aff.find(ka);
-         if (ia != open_aff.end() && try_join(ia->second, q, d0, (int)k, false)) { gi = ia->second; }
-         if (gi < 0)
-         {
-            auto ib = open_any.find(kb);
-            if (ib != open_any.end() && try_join(ib->second, q, d0, (int)k, true)) { gi = ib->second; }
-         }
-         if (gi < 0)
-         {
-            Run g{q.n, 1, q.c, d0, q.d1, 0, q.t1, 0, q.i0, {}};
-            for (int h = 0; h < q.c; h++) { g.s0.push_back(slot(d0, h)); }
-            gi = (int)out.size();
-            open_aff[ka] = gi;
-            out.push_back(g);
-            members.push_back({(int)k});
-         }
-         open_any[kb] = gi;
-      }
-      // Run order: by first partial slot (the slot locality of the entry order above) or by
-      // smallest dof (neighbouring workgroups of the pass then store neighbouring y lines: C5
-      // pass -10%, profiles/r3_ab_runorder.txt).  Which one is decided by the 128-B lines (y
-      // lines written + partial-slot lines read) that windows of 256 consecutive entries touch,
-      // the smaller total wins; ECM2_RUN_ORDER=slot|dof forces one.
-      std::vector<size_t> by_slot(out.size()), by_dof;
-      for (size_t g = 0; g < out.size(); g++) { by_slot[g] = g; }
-      {
-         std::vector<long> kmin(out.size(), LONG_MAX);
-         for (size_t g = 0; g < out.size(); g++)
-            for (int k : members[g])
-               for (int j = 0; j < r1s[k].n; j++) { kmin[g] = std::min<long>(kmin[g], dofs[r1s[k].i0 + j]); }
-         by_dof = by_slot;
-         std::stable_sort(by_dof.begin(), by_dof.end(), [&](size_t a, size_t b) { return kmin[a] < kmin[b]; });
-      }
-      auto lines_touched = [&](const std::vector<size_t> &go) {
-         long total = 0;
-         int in_window = 0;
-         std::vector<long> ids;
-         auto flush = [&] {
-            std::sort(ids.begin(), ids.end());
-            total += std::unique(ids.begin(), ids.end()) - ids.begin();
-            ids.clear();
-            in_window = 0;
-         };
-         for (size_t g : go)
-            for (int k : members[g])
-               for (int j = 0; j < r1s[k].n; j++)
-               {
-                  const int d = dofs[r1s[k].i0 + j];
-                  ids.push_back((long)d >> 4);
-                  for (int h = 0; h < cnt(d); h++) { ids.push_back((1l << 40) + (slot(d, h) >> 4)); }
-                  if (++in_window == 256) { flush(); }
-               }
-         flush();
-         return total;
-      };
-      // chain order: greedy, each next run the unplaced one sharing the most 128-B lines with the
-      // run placed last (ties and dead ends: the next unplaced run in slot order), so a face's edge
-      // runs follow its interior run and reuse its partial lines while they are in L2
-      auto chain_order = [&]() {
-         const size_t nr = out.size();
-         std::vector<std::vector<long>> rl(nr);
-         std::vector<long> all;
-         for (size_t g = 0; g < nr; g++)
-         {
-            for (int k : members[g])
-               for (int j = 0; j < r1s[k].n; j++)
-               {
-                  const int d = dofs[r1s[k].i0 + j];
-                  rl[g].push_back((long)d >> 4);
-                  for (int h = 0; h < cnt(d); h++) { rl[g].push_back((1l << 40) + (slot(d, h) >> 4)); }
-               }
-            std::sort(rl[g].begin(), rl[g].end());
-            rl[g].erase(std::unique(rl[g].begin(), rl[g].end()), rl[g].end());
-            all.insert(all.end(), rl[g].begin(), rl[g].end());
-         }
-         std::sort(all.begin(), all.end());
-         all.erase(std::unique(all.begin(), all.end()), all.end());
-         // line -> runs (CSR)
-         std::vector<int> loff(all.size() + 1, 0), lrun;
-         auto lid = [&](long v) { return (size_t)(std::lower_bound(all.begin(), all.end(), v) - all.begin()); };
-         std::vector<std::vector<int>> rli(nr);
-         for (size_t g = 0; g < nr; g++)
-            for (long v : rl[g])
-            {
-               const size_t i = lid(v);
-               rli[g].push_back((int)i);
-               loff[i + 1]++;
-            }
-         for (size_t i = 0; i < all.size(); i++) { loff[i + 1] += loff[i]; }
-         lrun.resize(loff.back());
-         {
-            std::vector<int> fill(loff.begin(), loff.end() - 1);
-            for (size_t g = 0; g < nr; g++)
-               for (int i : rli[g]) { lrun[fill[i]++] = (int)g; }
-         }
-         std::vector<char> placed(nr, 0);
-         std::vector<int> shared(nr, 0), touched;
-         std::vector<size_t> go;
-         go.reserve(nr);
-         size_t next_free = 0, cur = 0;
-         while (go.size() < nr)
-         {
-            if (go.empty() || placed[cur])
-            {
-               while (placed[next_free]) { next_free++; }
-               cur = next_free;
-            }
-            placed[cur] = 1;
-            go.push_back(cur);
-            size_t best = nr;
-            int bs = 0;
-            for (int i : rli[cur])
-               for (int q = loff[i]; q < loff[i + 1]; q++)
-               {
-                  const int g = lrun[q];
-                  if (placed[g]) { continue; }
-                  if (!shared[g]) { touched.push_back(g); }
-                  shared[g]++;
-               }
-            for (int g : touched)
-            {
-               if (shared[g] > bs || (shared[g] == bs && (size_t)g < best)) { bs = shared[g]; best = g; }
-               shared[g] = 0;
-            }
-            touched.clear();
-            cur = best < nr ? best : cur;  // cur placed: the next free run in slot order
-         }
-         return go;
-      };
-      const char *ro = std::getenv("ECM2_RUN_ORDER");
-      std::vector<size_t> by_chain;
-      int pick = 0;  // 0 slot, 1 dof, 2 chain
-      if (ro && std::string(ro) == "slot") { pick = 0; }
-      else if (ro && std::string(ro) == "dof") { pick = 1; }
-      else if (ro && std::string(ro) == "chain") { pick = 2; by_chain = chain_order(); }
-      else
-      {
-         by_chain = chain_order();
-         const long ls = lines_touched(by_slot), ld = lines_touched(by_dof), lc = lines_touched(by_chain);
-         pick = ld < ls ? 1 : 0;
-         if (lc < std::min(ls, ld)) { pick = 2; }
-         if (std::getenv("ECM2_PLAN_DUMP"))
-         {
-            std::fprintf(stderr, "plan range %d: lines touched by slot order %ld, dof order %ld, chain order %ld -> %s\n",
-                         range, ls, ld, lc, pick == 2 ? "chain" : pick ? "dof" : "slot");
-         }
-      }
-      const std::vector<size_t> &gord = pick == 2 ? by_chain : pick ? by_dof : by_slot;
-      for (size_t g : gord)
-      {
-         out[g].first = (int)order.size();
-         for (int k : members[g])
-            for (int j = 0; j < r1s[k].n; j++) { order.push_back(dofs[r1s[k].i0 + j]); }
-         runs.push_back(std::move(out[g]));
-      }
-      ECM2_VERIFY((int)order.size() == r1, ERR_INTERNAL, "run plan lost entries");
-   }
-   if (std::getenv("ECM2_PLAN_DUMP"))  // (diagnostic) run classes of the summation plan
-   {
-      std::map<std::tuple<int, int, int, int>, std::pair<long, long>> h;
-      for (const Run &g : runs)
-      {
-         auto &v = h[std::make_tuple(g.d1 == kExplicitDofs, g.c, g.n1, g.n2)];
-         v.first++;
-         v.second += (long)g.n1 * g.n2;
-      }
-      std::vector<std::pair<long, std::tuple<int, int, int, int>>> top;
-      for (auto &kv : h) { top.push_back({kv.second.first, kv.first}); }
-      std::sort(top.rbegin(), top.rend());
-      std::fprintf(stderr, "plan: %zu runs, %d entries\n", runs.size(), n_sh_);
-      for (size_t i = 0; i < top.size() && i < 30; i++)
-      {
-         const auto &k = top[i].second;
-         std::fprintf(stderr, "  explicit %d holders %d shape %dx%d: %ld runs, %ld entries\n", std::get<0>(k),
-                      std::get<1>(k), std::get<2>(k), std::get<3>(k), top[i].first, h[k].second);
-      }
-   }
-   std::vector<int> rdesc, rslots, blocks;
-   rdesc.reserve((runs.size() + 1) * 12);
-   for (const Run &g : runs)
-   {
-      // every entry of the run must be what the descriptor computes (checked, host side)
-      for (int j = 0; j < g.n1 * g.n2; j++)
-      {
-         const int a = j % g.n1, b = j / g.n1, d = order[g.first + j];
-         bool ok = (g.d1 == kExplicitDofs || d == g.dof0 + a * g.d1 + b * g.d2) && cnt(d) == g.c;
-         for (int h = 0; h < g.c && ok; h++) { ok = slot(d, h) == g.s0[h] + a * g.t1 + b * g.t2; }
-         ECM2_VERIFY(ok, ERR_INTERNAL, "run plan entry " << g.first + j << " does not match its run");
-      }
-      const bool ex = g.d1 == kExplicitDofs;  // shape bit 24: dofs from the entry list
-      ECM2_VERIFY(g.c < 256, ERR_UNSUPPORTED, "a dof with " << g.c << " holders");
-      int row[12] = {g.n1 | g.n2 << 8 | g.c << 16 | (ex ? 1 << 24 : 0), g.dof0, ex ? 0 : g.d1, ex ? 0 : g.d2,
-                     g.t1, g.t2, g.first, (int)rslots.size(), 0, 0, 0, 0};
-      for (int h = 0; h < g.c; h++)
-      {
-         if (h < 4) { row[8 + h] = g.s0[h]; }
-         rslots.push_back(g.s0[h]);
-      }
-      rdesc.insert(rdesc.end(), row, row + 12);
-   }
-   const int sentinel[12] = {1, 0, 0, 0, 0, 0, n_sh_, 0, 0, 0, 0, 0};
-   rdesc.insert(rdesc.end(), sentinel, sentinel + 12);
-   // blocks: whole runs, <= 256 entries each, never across the owned / ghost boundary
-   sh_nblk_owned_ = 0;
-   for (size_t r = 0; r < runs.size();)
-   {
-      const bool ghost = runs[r].first >= n_sh_owned_;
-      size_t e = r;
-      int n = 0;
-      while (e < runs.size() && (runs[e].first >= n_sh_owned_) == ghost && n + runs[e].n1 * runs[e].n2 <= 256)
-      {
-         n += runs[e].n1 * runs[e].n2;
-         e++;
-      }
-      bool ex = false;
-      for (size_t g = r; g < e; g++) { ex = ex || runs[g].d1 == kExplicitDofs; }
-      blocks.push_back((int)r);
-      blocks.push_back((int)e);
-      blocks.push_back(runs[r].first);
-      blocks.push_back(n | (ex ? 1 << 30 : 0));
-      if (!ghost) { sh_nblk_owned_++; }
-      r = e;
-   }
-   sh_nblk_ = (int)blocks.size() / 4;
-   n_runs_ = (long)runs.size();
-   sh_runs_.upload(rdesc, s);
-   sh_rslots_.upload(rslots.empty() ? std::vector<int>{0} : rslots, s);
-   sh_blocks_.upload(blocks.empty() ? std::vector<int>{0, 0, 0, 0} : blocks, s);
-   n_explicit_runs_ = 0;
-   for (const Run &g : runs) { n_explicit_runs_ += g.d1 == kExplicitDofs; }
-   sh_pdof_.upload(order.empty() ? std::vector<int>{0} : order, s);
-}
-
 void PAForm::set_kernel(int mode)
 {
    ECM2_VERIFY(mode >= KERNEL_AUTO && mode <= KERNEL_LINE, ERR_ARG, "unknown kernel mode " << mode);
@@ -663,9 +200,37 @@ void PAForm::set_kernel(int mode)
 
 static bool has_tpe(int D, int Q) { return (D == 2 && Q == 3) || (D == 3 && Q == 4); }
 
+// Assemble: the kernel and the qdata layout, the fused kernel's scatter plan (scatter_plan.hpp:
+// built on the host, uploaded here, kept until an input of it changes), then the quadrature data.
 void PAForm::assemble(hipStream_t s)
 {
    ECM2_VERIFY(enodes_.size() || jac_ || ne_ == 0, ERR_STATE, "assemble: no geometry set");
+   resolve_layout(s);
+   plan_tpe(s);
+   if (!btab_.size())
+   {
+      const BasisDev bd = make_basis_dev(basis_, D_, Q_);
+      btab_.upload(&bd, 1, s);
+   }
+   plan_line(s);
+   layout_.pos = layout_.blocked() ? pos_.data() : nullptr;
+   layout_.perm = layout_.blocked() ? perm_dev_.data() : nullptr;
+   if (!use_partials()) { part_.resize(0); }
+   else if (resolved_mode_ == KERNEL_LINE)
+   {
+      // [bricks' lattice slots | leftover elements' [e][nd] slots (when there are any)]
+      part_.resize(std::max<size_t>(1, (size_t)part_line_off_ + (n_left_ ? (size_t)ne_ * ND_ : 0)));
+   }
+   else { part_.resize((size_t)layout_.nblk() * part_stride_); }
+   choose_snapshot(s);
+   setup_qdata(s);
+   setup_marker_diagonal(s);
+   assembled_ = true;
+   gen_++;
+}
+
+void PAForm::resolve_layout(hipStream_t s)
+{
    resolved_mode_ = mode_;
    if (mode_ == KERNEL_AUTO)
    {
@@ -722,415 +287,82 @@ void PAForm::assemble(hipStream_t s)
          layout_.pw = have_mass_ ? 2 : 1;
       }
    }
+}
 
+void PAForm::upload_shared_plan(const SharedPlan &p, hipStream_t s)
+{
+   n_sh_ = p.n_sh;
+   n_sh_owned_ = p.n_sh_owned;
+   n_slots_ = p.n_slots;
+   n_runs_ = p.n_runs;
+   n_explicit_runs_ = p.n_explicit_runs;
+   sh_nblk_owned_ = p.nblk_owned;
+   sh_nblk_ = p.nblk;
+   sh_runs_.upload(p.runs, s);
+   sh_rslots_.upload(p.rslots.empty() ? std::vector<int>{0} : p.rslots, s);
+   sh_blocks_.upload(p.blocks.empty() ? std::vector<int>{0, 0, 0, 0} : p.blocks, s);
+   sh_pdof_.upload(p.pdof.empty() ? std::vector<int>{0} : p.pdof, s);
+}
+
+void PAForm::plan_tpe(hipStream_t s)
+{
    // the merge plan (cross-wave faces), the regular blocks and the partial-slot layout belong
    // to the qdata layout they were built for
    if (gmap_blk_.size() && plan_kind_ != layout_.kind) { gmap_blk_.resize(0); }
-   if (resolved_mode_ == KERNEL_TPE && !gmap_blk_.size() && ne_ > 0)
+   if (resolved_mode_ != KERNEL_TPE || gmap_blk_.size() || ne_ == 0) { return; }
+   plan_kind_ = layout_.kind;
+   const bool lattice_layout = layout_.kind == QLAYOUT_AFFINE || layout_.kind == QLAYOUT_TRILINEAR;
+   TpePlan p = build_tpe_plan(ne_, D_, ndofs_, n_owned_, gmap_host_, perm_host_, splits_, latency_from_, lattice_layout,
+                              plan_options_from_env());
+   n_treg_ = p.n_treg;
+   n_tlat_ = p.n_tlat;
+   treg_all_ = p.treg_all;
+   tlat_all_ = p.tlat_all;
+   part_stride_ = p.part_stride;
+   lmap_.upload(p.lmap, s);
+   treg_.upload(p.treg, s);
+   upload_shared_plan(p.shared, s);
+   gmap_blk_.upload(p.gmap_blk, s);
+   lane_flags_.upload(p.lane_flags, s);
+   pos_.upload(p.pos, s);
+   perm_dev_.upload(p.perm, s);
+   rowtab_.upload(kern::make_row_table(maps_), s);
+   drowtab_.upload(kern::make_diag_row_table(maps_), s);
+   ECM2_HIP(hipStreamSynchronize(s));  // the uploads read p
+   if (p.perm_derived)
    {
-      plan_kind_ = layout_.kind;
-      if (perm_host_.empty())
-      {
-         // no caller order: 4x4x4 face-linked bricks first (one per wave), per apply segment
-         std::vector<int> cuts{0};
-         for (int sp : splits_) { cuts.push_back(std::min(ne_, sp * kElemBlock)); }
-         cuts.push_back(ne_);
-         std::sort(cuts.begin(), cuts.end());
-         for (size_t k = 0; k + 1 < cuts.size(); k++)
-         {
-            const int e0 = cuts[k], n = cuts[k + 1] - cuts[k];
-            if (n <= 0) { continue; }
-            std::vector<int> sub(gmap_host_.begin() + (size_t)e0 * ND_, gmap_host_.begin() + (size_t)(e0 + n) * ND_);
-            for (int e : face_brick_order(n, D_, sub)) { perm_host_.push_back(e0 + e); }
-         }
-         perm_auto_ = true;
-      }
-      const int nblk = layout_.nblk();
-      std::vector<int> gint((size_t)ne_ * ND_), pos(ne_);
-      for (int i = 0; i < ne_; i++)
-      {
-         const int e = perm_host_.empty() ? i : perm_host_[i];
-         pos[e] = i;
-         std::copy(&gmap_host_[(size_t)e * ND_], &gmap_host_[(size_t)e * ND_] + ND_, &gint[(size_t)i * ND_]);
-      }
-      ECM2_VERIFY(ndofs_ < (1 << 30), ERR_UNSUPPORTED, "fused kernel supports < 2^30 dofs");
-      ECM2_VERIFY((size_t)nblk * ND_ * 64 < (1ull << 31), ERR_UNSUPPORTED, "too many elements for int slots");
-      std::vector<char> holds;
-      std::vector<int> fl, hcount;
-      // workgroups as the launches group them (4 blocks from each apply segment's start);
-      // waves of a workgroup may assemble shared faces through LDS (AFFINE kernels), except
-      // in segments launched with the one-block-per-workgroup latency kernel
-      std::vector<std::array<int, 3>> groups;
-      {
-         std::vector<int> seg{0, nblk};
-         for (int sp : splits_) { seg.push_back(std::max(0, std::min(nblk, sp))); }
-         std::sort(seg.begin(), seg.end());
-         seg.erase(std::unique(seg.begin(), seg.end()), seg.end());
-         const bool xw = layout_.kind == QLAYOUT_AFFINE || layout_.kind == QLAYOUT_TRILINEAR;
-         for (size_t k = 0; k + 1 < seg.size(); k++)
-         {
-            const bool lat = latency_from_ >= 0 && seg[k] >= latency_from_;
-            for (int b = seg[k]; b < seg[k + 1]; b += 4)
-            {
-               groups.push_back({b, std::min(b + 4, seg[k + 1]), (xw && !lat) ? 1 : 0});
-            }
-         }
-      }
-      build_merge_plan(ne_, D_, gint, ndofs_, holds, hcount, fl, groups);
-      // blocked map: dof | shared << 30 | sign << 31
-      std::vector<int> blk((size_t)nblk * ND_ * 64, 0);
-      for (int i = 0; i < ne_; i++)
-      {
-         const int b = i / 64, l = i % 64;
-         for (int a = 0; a < ND_; a++)
-         {
-            const int g = gint[(size_t)i * ND_ + a];
-            const unsigned d = (unsigned)(g >= 0 ? g : -1 - g);
-            const unsigned enc = d | ((hcount[d] > 1 ? 1u : 0u) << 30) | ((g < 0 ? 1u : 0u) << 31);
-            blk[((size_t)b * ND_ + a) * 64 + l] = (int)enc;
-         }
-      }
-      // Regular blocks (the AFFINE kernel): the block's 64 elements a 4x4x4 lattice brick
-      // (lane = ex + 4 ey + 16 ez) of a lattice-numbered region, d = base + X sx + Y sy + Z sz on
-      // the block's (4(D-1)+1)^3 lattice, every dof owned, no orientation signs, and the held
-      // shared dofs exactly those on the block faces a 6-bit mask names.  The kernel then reads
-      // 5 ints per block instead of 64 ND map entries (C4: 136 MB per Mult and a dependent load
-      // chain at the gather and the store).  Decided per block (a partitioned rank's interior
-      // blocks are regular, its boundary blocks are not); treg_all when every block is.
-      treg_.resize(0);
-      treg_all_ = false;
-      tlat_all_ = false;
-      n_treg_ = 0;
-      n_tlat_ = 0;
-      lmap_.resize(0);
-      const int ns = tpe_surface_points(D_);
-      std::vector<char> breg_ok(nblk, 0);
-      if (layout_.kind == QLAYOUT_AFFINE || layout_.kind == QLAYOUT_TRILINEAR)
-      {
-         const int L = 4 * (D_ - 1);
-         std::vector<int> reg((size_t)nblk * 8, 0);
-         auto ent = [&](int b, int l, int a) { return blk[((size_t)b * ND_ + a) * 64 + l]; };
-         auto faces = [&](int X, int Y, int Z) {
-            return (X == 0) | (X == L) << 1 | (Y == 0) << 2 | (Y == L) << 3 | (Z == 0) << 4 | (Z == L) << 5;
-         };
-         int nreg = 0;
-         for (int b = 0; b < nblk; b++)
-         {
-            // (blocks the latency kernel applies store [a][lane] slots: never regular)
-            bool regular = (long)(b + 1) * 64 <= ne_ && (latency_from_ < 0 || b < latency_from_);
-            auto dv = [&](int l, int a) { return ent(b, l, a) & 0x3fffffff; };
-            const int base = dv(0, 0), sx = dv(0, 1) - base, sy = dv(0, D_) - base, sz = dv(0, D_ * D_) - base;
-            int mask = 0;
-            for (int l = 0; l < 64 && regular; l++)
-               for (int a = 0; a < ND_ && regular; a++)
-               {
-                  const int X = (D_ - 1) * (l & 3) + a % D_, Y = (D_ - 1) * ((l >> 2) & 3) + (a / D_) % D_,
-                            Z = (D_ - 1) * (l >> 4) + a / (D_ * D_);
-                  const unsigned g = (unsigned)ent(b, l, a);
-                  const int d = (int)(g & 0x3fffffffu);
-                  regular = !(g >> 31) && d < n_owned_ && d == base + X * sx + Y * sy + Z * sz;
-                  // a held entry on exactly one face sets that face's bit
-                  const int f = faces(X, Y, Z);
-                  if (regular && holds[((size_t)b * 64 + l) * ND_ + a] && f && !(f & (f - 1)) && hcount[d] > 1)
-                  {
-                     mask |= f;
-                  }
-               }
-            for (int l = 0; l < 64 && regular; l++)
-               for (int a = 0; a < ND_ && regular; a++)
-               {
-                  if (!holds[((size_t)b * 64 + l) * ND_ + a]) { continue; }
-                  const int X = (D_ - 1) * (l & 3) + a % D_, Y = (D_ - 1) * ((l >> 2) & 3) + (a / D_) % D_,
-                            Z = (D_ - 1) * (l >> 4) + a / (D_ * D_);
-                  regular = (hcount[dv(l, a)] > 1) == ((faces(X, Y, Z) & mask) != 0);
-               }
-            if (!regular) { continue; }
-            int *r = &reg[(size_t)b * 8];
-            r[0] = base; r[1] = sx; r[2] = sy; r[3] = sz; r[4] = mask; r[7] = 1;
-            breg_ok[b] = 1;
-            nreg++;
-         }
-         n_treg_ = nreg;
-         // Lattice-slot blocks (flag 2): complete blocks whose dofs are not a lattice (the
-         // reference's entity numbering) but whose held shared entries all sit on distinct points
-         // of the block surface: their partial slots are face-grouped like a regular block's, so
-         // the summation plan's runs stay long (with the dofs from its entry list)
-         // Their dofs come from a block lattice map (tpe_lattice_slot order, one entry per lattice
-         // point): every entry of the block at one lattice point must encode the same dof, none
-         // with an orientation sign.
-         int nlat = 0;
-         const int NL = tpe_lattice_points(D_);
-         std::vector<int> lmap;
-         for (int b = 0; b < nblk; b++)
-         {
-            if (breg_ok[b] || (long)(b + 1) * 64 > ne_ || (latency_from_ >= 0 && b >= latency_from_)) { continue; }
-            std::vector<char> used(ns, 0);
-            std::vector<int> lm(NL, -1);
-            bool ok = true;
-            for (int l = 0; l < 64 && ok; l++)
-               for (int a = 0; a < ND_ && ok; a++)
-               {
-                  const int X = (D_ - 1) * (l & 3) + a % D_, Y = (D_ - 1) * ((l >> 2) & 3) + (a / D_) % D_,
-                            Z = (D_ - 1) * (l >> 4) + a / (D_ * D_);
-                  const int g = blk[((size_t)b * ND_ + a) * 64 + l];
-                  int &m = lm[tpe_lattice_slot(D_, X, Y, Z)];
-                  ok = !((unsigned)g >> 31) && (m < 0 || m == g);
-                  m = g;
-               }
-            for (int l = 0; l < 64 && ok; l++)
-               for (int a = 0; a < ND_ && ok; a++)
-               {
-                  if (!holds[((size_t)b * 64 + l) * ND_ + a]) { continue; }
-                  if (hcount[blk[((size_t)b * ND_ + a) * 64 + l] & 0x3fffffff] <= 1) { continue; }
-                  const int X = (D_ - 1) * (l & 3) + a % D_, Y = (D_ - 1) * ((l >> 2) & 3) + (a / D_) % D_,
-                            Z = (D_ - 1) * (l >> 4) + a / (D_ * D_);
-                  const int si = tpe_surface_index(D_, X, Y, Z);
-                  ok = si >= 0 && !used[si];
-                  if (ok) { used[si] = 1; }
-               }
-            if (!ok) { continue; }
-            reg[(size_t)b * 8 + 7] = 2;
-            breg_ok[b] = 2;
-            nlat++;
-            if (lmap.empty()) { lmap.assign((size_t)nblk * NL, 0); }
-            std::copy(lm.begin(), lm.end(), lmap.begin() + (size_t)b * NL);
-         }
-         n_tlat_ = nlat;
-         lmap_.resize(0);
-         if (nlat) { lmap_.upload(lmap, s); }
-         if (nreg || nlat)
-         {
-            treg_.upload(reg, s);
-            treg_all_ = nreg == nblk && (latency_from_ < 0 || latency_from_ >= nblk);
-            tlat_all_ = nlat == nblk && (latency_from_ < 0 || latency_from_ >= nblk);
-         }
-      }
-      part_stride_ = treg_all_ || tlat_all_ ? ns : ND_ * 64;
-      {
-         // partial slots: [blk][a][lane]; on regular blocks [blk][face-grouped surface index of
-         // the block lattice] (tpe_surface_index: a face's two holders list it at the same
-         // offset, so the summation pass reads both holders' runs contiguously)
-         std::vector<int> hdof, hslot;
-         for (int b = 0; b < nblk; b++)
-            for (int a = 0; a < ND_; a++)
-               for (int l = 0; l < 64; l++)
-               {
-                  if (!holds[((size_t)b * 64 + l) * ND_ + a]) { continue; }
-                  const int d = blk[((size_t)b * ND_ + a) * 64 + l] & 0x3fffffff;
-                  if (hcount[d] > 1)
-                  {
-                     hdof.push_back(d);
-                     if (breg_ok[b])
-                     {
-                        const int X = (D_ - 1) * (l & 3) + a % D_, Y = (D_ - 1) * ((l >> 2) & 3) + (a / D_) % D_,
-                                  Z = (D_ - 1) * (l >> 4) + a / (D_ * D_);
-                        const int si = tpe_surface_index(D_, X, Y, Z);
-                        ECM2_VERIFY(si >= 0, ERR_INTERNAL, "block " << b << ": interior lattice point shared");  // (checked)
-                        hslot.push_back(b * part_stride_ + si);
-                     }
-                     else { hslot.push_back(b * part_stride_ + a * 64 + l); }
-                  }
-               }
-         // the plan wants each dof's holders in ascending slot order
-         std::vector<size_t> ord(hslot.size());
-         for (size_t i = 0; i < ord.size(); i++) { ord[i] = i; }
-         std::sort(ord.begin(), ord.end(), [&](size_t p, size_t q) { return hslot[p] < hslot[q]; });
-         std::vector<int> hd(ord.size()), hs(ord.size());
-         for (size_t i = 0; i < ord.size(); i++) { hd[i] = hdof[ord[i]]; hs[i] = hslot[ord[i]]; }
-         build_shared_plan(hcount, hd, hs, s);
-      }
-      gmap_blk_.upload(blk, s);
-      lane_flags_.upload(fl, s);
-      pos_.upload(pos, s);
-      std::vector<int> perm(ne_);
-      for (int e = 0; e < ne_; e++) { perm[pos[e]] = e; }
-      perm_dev_.upload(perm, s);
-      rowtab_.upload(kern::make_row_table(maps_), s);
-      drowtab_.upload(kern::make_diag_row_table(maps_), s);
-      ECM2_HIP(hipStreamSynchronize(s));
+      perm_host_ = std::move(p.perm);
+      perm_auto_ = true;
    }
-   if (!btab_.size())
-   {
-      const BasisDev bd = make_basis_dev(basis_, D_, Q_);
-      btab_.upload(&bd, 1, s);
-   }
-   if (resolved_mode_ == KERNEL_LINE && !gmap_line_.size() && ne_ > 0)
-   {
-      // Bricks of 2 x 2 x bz elements (deterministic scatter, both integrators) take every
-      // element they can; the leftovers run the per-element line kernel, listed per
-      // 64-element block (apply_blocks ranges map to list ranges).  Then the encoded maps and
-      // the deterministic-scatter plan over the holding entries: the bricks' lattice points,
-      // the leftovers' entries.
-      ECM2_VERIFY(ndofs_ < (1 << 30), ERR_UNSUPPORTED, "fused kernel supports < 2^30 dofs");
-      ECM2_VERIFY((size_t)ne_ * ND_ < (1ull << 31) && ne_ < (1 << 24), ERR_UNSUPPORTED,
-                  "too many elements for the line kernel's chunk table");
-      auto dofv = [](int g) { return g >= 0 ? g : -1 - g; };
-      const int nblk = layout_.nblk();
-      // default 2 x 2 x 1 (C5, profiles/ab_brick.sh: 0.861 ms against 1.018 ms per element and
-      // 1.114 ms for 2 x 2 x 2)
-      int bz = (scatter_ == SCATTER_PARTIALS && have_mass_ && have_diff_) ? (line_bricks_ >= 0 ? line_bricks_ : 1) : 0;
-      if (bz == 2 && !kern::has_brick(D_, Q_, 2)) { bz = 1; }
-      if (bz == 1 && !kern::has_brick(D_, Q_, 1)) { bz = 0; }
-      std::vector<int> belem;
-      std::vector<char> in_brick(ne_, 0);
-      if (bz)
-      {
-         std::vector<int> seg(ne_, 0);
-         for (int e = 0; e < ne_; e++)
-         {
-            for (int sp : splits_) { seg[e] += (e / kElemBlock >= sp); }
-         }
-         find_bricks(ne_, D_, gmap_host_, bz, seg, belem, in_brick);
-      }
-      const int nbe = 4 * (bz ? bz : 1);
-      n_bricks_ = bz ? (int)(belem.size() / nbe) : 0;
-      brick_bz_ = n_bricks_ ? bz : 0;
-      brick_np_ = brick_bz_ ? kern::brick_points(D_, brick_bz_) : 0;
-      const int LX = 2 * D_ - 1, LY = LX;
-      // lattice map of each brick (dof per lattice point; internal faces coincide by construction)
-      std::vector<int> bdof((size_t)n_bricks_ * brick_np_, -1);
-      for (int k = 0; k < n_bricks_; k++)
-         for (int elt = 0; elt < nbe; elt++)
-         {
-            const int e = belem[(size_t)k * nbe + elt], ex = elt & 1, ey = (elt >> 1) & 1, ez = elt >> 2;
-            for (int dz = 0; dz < D_; dz++)
-               for (int dy = 0; dy < D_; dy++)
-                  for (int dx = 0; dx < D_; dx++)
-                  {
-                     const int p = ((ez * (D_ - 1) + dz) * LY + ey * (D_ - 1) + dy) * LX + ex * (D_ - 1) + dx;
-                     const int d = dofv(gmap_host_[(size_t)e * ND_ + (dz * D_ + dy) * D_ + dx]);
-                     int &b = bdof[(size_t)k * brick_np_ + p];
-                     ECM2_VERIFY(b < 0 || b == d, ERR_INTERNAL, "brick " << k << " lattice point " << p
-                                                                    << " holds two dofs");
-                     b = d;
-                  }
-         }
-      std::vector<int> lelem, coff(nblk + 1, 0), boff(nblk + 1, 0);
-      std::vector<char> holds((size_t)ne_ * ND_, 0);
-      for (int bk = 0; bk < nblk; bk++)
-      {
-         for (int e = bk * 64; e < std::min(ne_, bk * 64 + 64); e++)
-         {
-            if (in_brick[e]) { continue; }
-            lelem.push_back(e);
-            for (int a = 0; a < ND_; a++) { holds[(size_t)e * ND_ + a] = 1; }
-         }
-         coff[bk + 1] = (int)lelem.size();
-      }
-      const int n_left = (int)lelem.size();
-      for (int k = 0, bk = 0; bk < nblk; bk++)
-      {
-         while (k < n_bricks_ && belem[(size_t)k * nbe] / kElemBlock == bk) { k++; }
-         boff[bk + 1] = k;
-      }
-      ECM2_VERIFY(boff[nblk] == n_bricks_, ERR_INTERNAL, "bricks not ordered by first element");
-      std::vector<int> hcount(ndofs_, 0);
-      for (int d : bdof) { hcount[d]++; }
-      for (size_t i = 0; i < gmap_host_.size(); i++) { if (holds[i]) { hcount[dofv(gmap_host_[i])]++; } }
-      auto encode = [&](int d, bool neg) {
-         return (int)((unsigned)d | ((hcount[d] > 1 ? 1u : 0u) << 30) | ((neg ? 1u : 0u) << 31));
-      };
-      // brick partial slots: [brick][face-grouped surface index]; only surface points can be
-      // shared (a brick holds its interior lattice points alone: checked)
-      const int nsurf = brick_bz_ ? brick_surface_points(D_, brick_bz_) : 0;
-      part_line_off_ = (long)n_bricks_ * nsurf;
-      std::vector<int> enc(gmap_host_.size()), benc(bdof.size()), hdof, hslot;
-      std::vector<long> bslot;
-      for (size_t i = 0; i < bdof.size(); i++)
-      {
-         benc[i] = encode(bdof[i], false);
-         if (hcount[bdof[i]] > 1)
-         {
-            const int k = (int)(i / brick_np_), p = (int)(i % brick_np_);
-            const int si = brick_surface_index(D_, brick_bz_, p % LX, (p / LX) % LY, p / (LX * LY));
-            ECM2_VERIFY(si >= 0, ERR_INTERNAL, "brick " << k << ": interior lattice point " << p << " is shared");
-            hdof.push_back(bdof[i]);
-            bslot.push_back((long)k * nsurf + si);
-         }
-      }
-      // the plan wants the holders in ascending slot order
-      {
-         std::vector<size_t> ord(bslot.size());
-         for (size_t i = 0; i < ord.size(); i++) { ord[i] = i; }
-         std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return bslot[a] < bslot[b]; });
-         std::vector<int> hd(ord.size());
-         hslot.resize(ord.size());
-         for (size_t i = 0; i < ord.size(); i++)
-         {
-            hd[i] = hdof[ord[i]];
-            hslot[i] = (int)bslot[ord[i]];
-         }
-         hdof.swap(hd);
-      }
-      ECM2_VERIFY(part_line_off_ + (long)nblk * ND_ * 64 < (1l << 31), ERR_UNSUPPORTED, "too many partial slots");
-      for (size_t i = 0; i < gmap_host_.size(); i++)
-      {
-         const int g = gmap_host_[i];
-         const int d = dofv(g);
-         enc[i] = encode(d, g < 0);
-         if (holds[i] && hcount[d] > 1)
-         {
-            hdof.push_back(d);
-            hslot.push_back((int)(part_line_off_ + (long)i));
-         }
-      }
-      build_shared_plan(hcount, hdof, hslot, s);
-      // Regular bricks: every brick's lattice map an affine function of the lattice point
-      // (d = base + X sx + Y sy + Z sz, a lattice-numbered mesh) and its shared points exactly
-      // those on the brick faces other holders touch (one face-mask bit per face) -- the kernel
-      // then computes dofs and shared flags from 5 ints per brick instead of reading the map
-      breg_.resize(0);
-      if (n_bricks_ && n_owned_ == ndofs_)
-      {
-         const int LZ = brick_bz_ * (D_ - 1) + 1;
-         std::vector<int> reg((size_t)n_bricks_ * 8, 0);
-         bool regular = true;
-         for (int k = 0; k < n_bricks_ && regular; k++)
-         {
-            const int *b = &bdof[(size_t)k * brick_np_];
-            const int base = b[0], sx = b[1] - base, sy = b[LX] - base, sz = b[LX * LY] - base;
-            auto faces = [&](int X, int Y, int Z) {
-               return (X == 0) | (X == LX - 1) << 1 | (Y == 0) << 2 | (Y == LY - 1) << 3 | (Z == 0) << 4 |
-                      (Z == LZ - 1) << 5;
-            };
-            // face bit = sharing of a point inside that face (on no other face)
-            const int cx = LX / 2, cy = LY / 2, cz = LZ / 2;
-            const int probe[6][3] = {{0, cy, cz}, {LX - 1, cy, cz}, {cx, 0, cz}, {cx, LY - 1, cz}, {cx, cy, 0}, {cx, cy, LZ - 1}};
-            int mask = 0;
-            for (int f = 0; f < 6; f++)
-            {
-               const int p = (probe[f][2] * LY + probe[f][1]) * LX + probe[f][0];
-               if (hcount[b[p]] > 1) { mask |= 1 << f; }
-            }
-            for (int p = 0; p < brick_np_ && regular; p++)
-            {
-               const int X = p % LX, Y = (p / LX) % LY, Z = p / (LX * LY);
-               regular = b[p] == base + X * sx + Y * sy + Z * sz &&
-                         (hcount[b[p]] > 1) == ((faces(X, Y, Z) & mask) != 0);
-            }
-            int *r = &reg[(size_t)k * 8];
-            r[0] = base; r[1] = sx; r[2] = sy; r[3] = sz; r[4] = mask;
-         }
-         if (regular) { breg_.upload(reg, s); }
-      }
-      gmap_line_.upload(enc, s);
-      lelem_.upload(lelem.empty() ? std::vector<int>{0} : lelem, s);
-      lelem_off_ = coff;
-      belem_.upload(belem, s);
-      bmap_.upload(benc, s);
-      brick_off_ = boff;
-      n_left_ = n_left;
-      ECM2_HIP(hipStreamSynchronize(s));
-   }
-   layout_.pos = layout_.blocked() ? pos_.data() : nullptr;
-   layout_.perm = layout_.blocked() ? perm_dev_.data() : nullptr;
-   if (!use_partials()) { part_.resize(0); }
-   else if (resolved_mode_ == KERNEL_LINE)
-   {
-      // [bricks' lattice slots | leftover elements' [e][nd] slots (when there are any)]
-      part_.resize(std::max<size_t>(1, (size_t)part_line_off_ + (n_left_ ? (size_t)ne_ * ND_ : 0)));
-   }
-   else { part_.resize((size_t)layout_.nblk() * part_stride_); }
+}
+
+void PAForm::plan_line(hipStream_t s)
+{
+   if (resolved_mode_ != KERNEL_LINE || gmap_line_.size() || ne_ == 0) { return; }
+   // default 2 x 2 x 1 (C5, profiles/ab_brick.sh: 0.861 ms against 1.018 ms per element and
+   // 1.114 ms for 2 x 2 x 2)
+   int bz = (scatter_ == SCATTER_PARTIALS && have_mass_ && have_diff_) ? (line_bricks_ >= 0 ? line_bricks_ : 1) : 0;
+   if (bz == 2 && !kern::has_brick(D_, Q_, 2)) { bz = 1; }
+   if (bz == 1 && !kern::has_brick(D_, Q_, 1)) { bz = 0; }
+   LinePlan p = build_line_plan(ne_, D_, ndofs_, n_owned_, gmap_host_, splits_, bz, plan_options_from_env());
+   n_bricks_ = p.n_bricks;
+   brick_bz_ = p.brick_bz;
+   brick_np_ = p.brick_np;
+   n_left_ = p.n_left;
+   part_line_off_ = p.part_line_off;
+   upload_shared_plan(p.shared, s);
+   breg_.upload(p.breg, s);
+   gmap_line_.upload(p.gmap_line, s);
+   lelem_.upload(p.lelem.empty() ? std::vector<int>{0} : p.lelem, s);
+   belem_.upload(p.belem, s);
+   bmap_.upload(p.bmap, s);
+   ECM2_HIP(hipStreamSynchronize(s));  // the uploads read p
+   lelem_off_ = std::move(p.lelem_off);
+   brick_off_ = std::move(p.brick_off);
+}
+
+void PAForm::choose_snapshot(hipStream_t s)
+{
    // Coefficient snapshot (k_apply_tpe_ts): the diffusion coefficient a law of an H1 field on this
    // space (GridFunctionCoefficient, AffineGridFunctionCoefficient, the perfusion law), AFFINE
    // geometry, p = 2, every block a lattice brick, no attribute marker on the diffusion integrator.
@@ -1176,9 +408,12 @@ void PAForm::assemble(hipStream_t s)
          kern::affine_snapshot_lattice(layout_.nblk(), nlp, lmap_.data(), cdiff_.lvec, A, B, tsnap_.data(), s);
       }
    }
-   setup_qdata(s);
-   // The marker diagonal's element weights (assemble_diagonal), from the Assemble-time attributes
-   // (the reference reads them in SetupRestrictionOperators, bilinearform_ext.cpp:269)
+}
+
+// The marker diagonal's element weights (assemble_diagonal), from the Assemble-time attributes
+// (the reference reads them in SetupRestrictionOperators, bilinearform_ext.cpp:269)
+void PAForm::setup_marker_diagonal(hipStream_t s)
+{
    diag_integ_ = -1;
    diag_w_.resize(0);
    if (order_added_.size() == 2 && marked_[order_added_[1]])
@@ -1194,8 +429,6 @@ void PAForm::assemble(hipStream_t s)
          ECM2_HIP(hipStreamSynchronize(s));  // ws is a host temporary
       }
    }
-   assembled_ = true;
-   gen_++;
 }
 
 std::vector<double> PAForm::marker_weights(int k) const

@@ -11,6 +11,10 @@
 // Ownership follows the reference: the form owns qdata and its work vectors;
 // x / y are caller-owned device arrays; all work is enqueued on the caller's
 // stream (the reference uses the null stream, forall.hpp:782).
+//
+// The fused kernels' scatter planning (element order, merge flags, dof maps, lattice blocks and
+// bricks, partial slots, the summation plan) is host-only code in scatter_plan.hpp; this class
+// uploads what those functions return and keeps the scalars the launches need.
 #pragma once
 
 #include "common.hpp"
@@ -23,6 +27,8 @@
 
 namespace ecm2
 {
+
+struct SharedPlan;  // scatter_plan.hpp
 
 enum KernelMode : int
 {
@@ -188,10 +194,15 @@ private:
    void ensure_work(hipStream_t s);
    void record_start(hipStream_t s);
    void record_stop(hipStream_t s);
-   // second pass of the deterministic scatter from the shared holding entries
-   // (hdof[i], hslot[i]) in ascending slot order and the per-dof holder counts
-   void build_shared_plan(const std::vector<int> &hcount, const std::vector<int> &hdof,
-                          const std::vector<int> &hslot, hipStream_t s);
+   // assemble()'s steps, in order: kernel mode and qdata layout; the fused kernel's scatter plan
+   // (built by scatter_plan.hpp's host functions unless the cached one still holds, then uploaded);
+   // the coefficient snapshot; setup_qdata; the marker diagonal's weights
+   void resolve_layout(hipStream_t s);
+   void plan_tpe(hipStream_t s);
+   void plan_line(hipStream_t s);
+   void upload_shared_plan(const SharedPlan &p, hipStream_t s);
+   void choose_snapshot(hipStream_t s);
+   void setup_marker_diagonal(hipStream_t s);
    ApplyArgs apply_args(const double *x, const double *xg, double *y, double *yg, int b0,
                         int b1) const;
    // qdata of the integrators present (resized, padding cleared, coefficients projected, setup
