@@ -1031,15 +1031,15 @@ k_diag_sf(const int *__restrict__ pos, int kind, int ne, const int *__restrict__
 }
 
 template <int D, int Q, bool MASS, bool DIFF>
-void launch_line_mdq(const ApplyArgs &a, hipStream_t s)
+void launch_line_mdq(const ApplyArgs &a, const LineArgs &l, hipStream_t s)
 {
-   ECM2_VERIFY(a.lelem && a.lelem_off, ERR_INTERNAL, "line kernel needs its element list");
-   const int c0 = a.lelem_off[a.blk_begin], c1 = a.lelem_off[a.blk_end];
+   ECM2_VERIFY(l.lelem && l.lelem_off, ERR_INTERNAL, "line kernel needs its element list");
+   const int c0 = l.lelem_off[a.blk_begin], c1 = l.lelem_off[a.blk_end];
    if (c1 <= c0) { return; }
    const dim3 grid(c1 - c0), block(64);
 #define ECM2_LINE(GG)                                                                                     \
-   hipLaunchKernelGGL((k_apply_line<D, Q, MASS, DIFF, GG>), grid, block, 0, s, c0, c1, a.lelem, a.n_owned,   \
-                      a.gmap, a.qdd, a.qdm, a.x, a.xg, a.y, a.yg, a.btab, a.part, a.qp)
+   hipLaunchKernelGGL((k_apply_line<D, Q, MASS, DIFF, GG>), grid, block, 0, s, c0, c1, l.lelem, a.n_owned,   \
+                      a.gmap, a.qdd, a.qdm, a.x, a.xg, a.y, a.yg, l.btab, a.part, a.qp)
    if (a.kind == QLAYOUT_AFFINE_E || a.kind == QLAYOUT_TRILINEAR_E)
    {
       if constexpr (DIFF)
@@ -1056,45 +1056,45 @@ void launch_line_mdq(const ApplyArgs &a, hipStream_t s)
 }
 
 template <int D, int Q>
-void launch_line_dq(bool mass, bool diff, const ApplyArgs &a, hipStream_t s)
+void launch_line_dq(bool mass, bool diff, const ApplyArgs &a, const LineArgs &l, hipStream_t s)
 {
-   if (mass && diff) { launch_line_mdq<D, Q, true, true>(a, s); }
-   else if (mass) { launch_line_mdq<D, Q, true, false>(a, s); }
-   else if (diff) { launch_line_mdq<D, Q, false, true>(a, s); }
+   if (mass && diff) { launch_line_mdq<D, Q, true, true>(a, l, s); }
+   else if (mass) { launch_line_mdq<D, Q, true, false>(a, l, s); }
+   else if (diff) { launch_line_mdq<D, Q, false, true>(a, l, s); }
 }
 
 template <int D, int BZ>
-void launch_brick(const ApplyArgs &a, hipStream_t s)
+void launch_brick(const ApplyArgs &a, const LineArgs &l, hipStream_t s)
 {
    constexpr int Q = D + 1;
-   const int k0 = a.brick_off[a.blk_begin], k1 = a.brick_off[a.blk_end];
+   const int k0 = l.brick_off[a.blk_begin], k1 = l.brick_off[a.blk_end];
    if (k1 <= k0) { return; }
-   ECM2_VERIFY(a.part_brick, ERR_INTERNAL, "brick kernel needs its partial slots");
+   ECM2_VERIFY(l.part_brick, ERR_INTERNAL, "brick kernel needs its partial slots");
    const bool split = a.xg || a.yg;
    const int g = a.kind == QLAYOUT_AFFINE_E ? 1 : a.kind == QLAYOUT_TRILINEAR_E ? 2 : 0;
    ECM2_VERIFY(g == 0 || a.pw == 2, ERR_INTERNAL, "bricks need both integrators");
    const dim3 grid(k1 - k0), block(BrickShapeC<D, Q, BZ>::NT);
 #define ECM2_BRICK(SP, GG, RG)                                                                             \
-   hipLaunchKernelGGL((k_apply_brick_c<D, Q, BZ, SP, GG, RG>), grid, block, 0, s, k0, k1, a.belem, a.bmap,    \
-                      a.breg, a.n_owned, a.qdd, a.qdm, a.x, a.xg, a.y, a.yg, a.btab, a.part_brick, a.qp)
+   hipLaunchKernelGGL((k_apply_brick_c<D, Q, BZ, SP, GG, RG>), grid, block, 0, s, k0, k1, l.belem, l.bmap,    \
+                      l.breg, a.n_owned, a.qdd, a.qdm, a.x, a.xg, a.y, a.yg, l.btab, l.part_brick, a.qp)
 #define ECM2_BRICK_G(SP, RG)                    \
    if (g == 1 && a.cdiag) { ECM2_BRICK(SP, 3, RG); } \
    else if (g == 1) { ECM2_BRICK(SP, 1, RG); }  \
    else if (g == 2) { ECM2_BRICK(SP, 2, RG); }  \
    else { ECM2_BRICK(SP, 0, RG); }
    if (split) { ECM2_BRICK_G(true, false) }
-   else if (a.breg) { ECM2_BRICK_G(false, true) }
+   else if (l.breg) { ECM2_BRICK_G(false, true) }
    else { ECM2_BRICK_G(false, false) }
 #undef ECM2_BRICK_G
 #undef ECM2_BRICK
 }
 
-void apply_brick(int D, int Q, const ApplyArgs &a, hipStream_t s)
+void apply_brick(int D, int Q, const ApplyArgs &a, const LineArgs &l, hipStream_t s)
 {
 #define ECM2_BRICK_CASE(DD, BZ)                                         \
-   if (D == DD && Q == DD + 1 && a.brick_bz == BZ)                      \
+   if (D == DD && Q == DD + 1 && l.brick_bz == BZ)                      \
    {                                                                    \
-      launch_brick<DD, BZ>(a, s);                                       \
+      launch_brick<DD, BZ>(a, l, s);                                    \
       ECM2_HIP(hipGetLastError());                                      \
       return;                                                           \
    }
@@ -1106,7 +1106,7 @@ void apply_brick(int D, int Q, const ApplyArgs &a, hipStream_t s)
    ECM2_BRICK_CASE(6, 2)
    ECM2_BRICK_CASE(7, 1)
 #undef ECM2_BRICK_CASE
-   ECM2_VERIFY(false, ERR_UNSUPPORTED, "no brick kernel for D1D=" << D << " Q1D=" << Q << " bz=" << a.brick_bz);
+   ECM2_VERIFY(false, ERR_UNSUPPORTED, "no brick kernel for D1D=" << D << " Q1D=" << Q << " bz=" << l.brick_bz);
 }
 
 } // namespace
@@ -1129,19 +1129,19 @@ bool has_brick(int D, int Q, int bz)
 
 int brick_points(int D, int bz) { return (2 * D - 1) * (2 * D - 1) * (bz * (D - 1) + 1); }
 
-void apply_line(int D, int Q, bool mass, bool diff, const ApplyArgs &a, hipStream_t s)
+void apply_line(int D, int Q, bool mass, bool diff, const ApplyArgs &a, const LineArgs &l, hipStream_t s)
 {
    if (a.ne == 0) { return; }
-   ECM2_VERIFY(a.btab, ERR_INTERNAL, "line kernel needs the device basis table");
-   if (a.brick_bz)
+   ECM2_VERIFY(l.btab, ERR_INTERNAL, "line kernel needs the device basis table");
+   if (l.brick_bz)
    {
       ECM2_VERIFY(mass && diff, ERR_INTERNAL, "bricks need both integrators");
-      apply_brick(D, Q, a, s);
+      apply_brick(D, Q, a, l, s);
    }
 #define ECM2_LINE_CASE(DD, QQ)                                        \
    if (D == DD && Q == QQ)                                            \
    {                                                                  \
-      launch_line_dq<DD, QQ>(mass, diff, a, s);                       \
+      launch_line_dq<DD, QQ>(mass, diff, a, l, s);                    \
       ECM2_HIP(hipGetLastError());                                    \
       return;                                                         \
    }

@@ -17,13 +17,6 @@ namespace
 {
 using namespace dev;
 
-// ECM2_SF_W3 (an A/B build): k_apply_tpe_sf (AFFINE / map-addressed blocks, what a
-// z-slab rank runs) compiled for three waves per SIMD -- 168 VGPRs, 53,248 B of LDS per workgroup.
-#ifndef ECM2_SF_W3
-#define ECM2_SF_W3 0
-#endif
-constexpr bool kSfW3 = ECM2_SF_W3;
-
 // Rows per wave of the LDS region the cross-wave face exchange uses (3 faces of D x D).
 template <int D>
 struct XwaveRows
@@ -59,7 +52,7 @@ struct TpeReg
 // MAYREG: regf may be nonzero (per block).
 // XR: rows per wave of xb (a kernel whose waves stage more than XwaveRows rows passes its stride, so
 // a wave's sends land in its own region while the other waves may still read theirs).
-template <int D, bool SPLIT, bool SIGNS, bool XW, bool MAYREG = false, int XR = XwaveRows<D>::R, bool XREUSE = false>
+template <int D, bool SPLIT, bool SIGNS, bool XW, bool MAYREG = false, int XR = XwaveRows<D>::R>
 __device__ __forceinline__ void tpe_assemble_store(double (&Yo)[D * D * D], const int *__restrict__ mp, int fl,
                                                    int blk, int lane, bool active, int n_owned,
                                                    double *__restrict__ y, double *__restrict__ yg,
@@ -68,10 +61,7 @@ __device__ __forceinline__ void tpe_assemble_store(double (&Yo)[D * D * D], cons
                                                    const int *__restrict__ lm = nullptr)
 {
    constexpr int ND = D * D * D;
-   // XREUSE: the z faces reuse the x faces' rows (the y merge's barrier orders every wave's x-face
-   // reads before any z-face write), so 2 D^2 rows per wave suffice
-   static_assert(XR >= (XREUSE ? 2 * D * D : XwaveRows<D>::R), "staging rows");
-   auto xrow = [](int dir) { return (XREUSE ? (dir & 1) : dir) * D * D; };
+   static_assert(XR >= XwaveRows<D>::R, "staging rows");
    const bool rr = MAYREG && regf == 1, rs = MAYREG && regf != 0, rl = MAYREG && regf == 2;
    // A lattice-map block's store entries are loaded here, before the face merges: their latency
    // (the map left L2 while the block computed) overlaps the shuffles and barriers instead of
@@ -107,7 +97,7 @@ __device__ __forceinline__ void tpe_assemble_store(double (&Yo)[D * D * D], cons
 #pragma unroll
          for (int j = 0; j < D; j++)
 #pragma unroll
-            for (int i = 0; i < D; i++) { xb[((w * XR) + xrow(dir) + j * D + i) * 64 + lane] = Yo[face(0, i, j)]; }
+            for (int i = 0; i < D; i++) { xb[((w * XR) + dir * D * D + j * D + i) * 64 + lane] = Yo[face(0, i, j)]; }
       }
       if (wave_on)
       {
@@ -132,7 +122,7 @@ __device__ __forceinline__ void tpe_assemble_store(double (&Yo)[D * D * D], cons
 #pragma unroll
                for (int i = 0; i < D; i++)
                {
-                  Yo[face(D - 1, i, j)] += xb[((pw * XR) + xrow(dir) + j * D + i) * 64 + lane - 3 * delta];
+                  Yo[face(D - 1, i, j)] += xb[((pw * XR) + dir * D * D + j * D + i) * 64 + lane - 3 * delta];
                }
          }
       }
@@ -355,7 +345,7 @@ k_apply_tpe_pf(int ne, int blk_begin, int blk_end, int n_owned, const int *__res
 // 349-362) and the mass setup's W alpha det J, never stored.
 // PW: point values per quadrature point (2: the pair; 1: a diffusion-only form's W beta [/ det J]).
 template <int D, int Q, bool SPLIT, int RM, bool TL = false, int PW = 2>
-__global__ void __launch_bounds__(256, (kSfW3 && !TL) ? 3 : 1)
+__global__ void __launch_bounds__(256, 1)
 k_apply_tpe_sf(int ne, int blk_begin, int blk_end, int n_owned, const int *__restrict__ gmap,
                const double *__restrict__ qdd, const double *__restrict__ qdm,
                const double *__restrict__ x, const double *__restrict__ xg,
@@ -364,19 +354,11 @@ k_apply_tpe_sf(int ne, int blk_begin, int blk_end, int n_owned, const int *__res
                int pstride, const int *__restrict__ lmap, const QPts qp)
 {
    constexpr int ND = D * D * D, NQ = Q * Q * Q, NR = Q * Q, WPG = 4;
-   // W3 (kSfW3, the three-waves-per-SIMD build): the last x value stays in a register and the face
-   // exchange reuses its rows, so three workgroups fit a CU's LDS (26 rows: 159,744 B)
-   constexpr bool W3 = kSfW3 && !TL;
-   constexpr int XR = W3 ? (ND - 1 > 2 * D * D ? ND - 1 : 2 * D * D) : XwaveRows<D>::R;
-   constexpr int XL = W3 ? ND - 1 : ND;  // x values staged in LDS
+   constexpr int XR = XwaveRows<D>::R;
    __shared__ double sX[WPG][XR][64];  // gathered x; then the cross-wave face exchange
    const int lane = threadIdx.x & 63;
    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: block data in SGPRs
-   double xl = 0.0;                                                  // W3: x value ND - 1
-   auto put_x = [&](int a, double v) {
-      if (a < XL) { sX[w][a][lane] = v; }
-      else { xl = v; }
-   };
+   auto put_x = [&](int a, double v) { sX[w][a][lane] = v; };
    // (round-robin dispatch: the XCD-contiguous order of the lattice kernels is 2.6% slower here,
    // profiles/r5/ab_xcd.txt)
    const int blk = blk_begin + (int)blockIdx.x * WPG + w;
@@ -421,14 +403,14 @@ k_apply_tpe_sf(int ne, int blk_begin, int blk_end, int n_owned, const int *__res
       // are in flight instead of 4 (profiles/r2_ab_pf2.txt: C4 kernel -4.3%); the plane loop is
       // unrolled so the rotation is static.  Map-addressed kernels (RM = 0) keep the ping-pong:
       // unrolled, their register demand exceeds 256 VGPRs; at p = 1 the third buffer costs a wave/SIMD.
-      constexpr bool PF2 = RM != 0 && D == 3 && !TL && !W3;  // TL: the runtime plane loop keeps the geometry live once
+      constexpr bool PF2 = RM != 0 && D == 3 && !TL;  // TL: the runtime plane loop keeps the geometry live once
       v2d ra[PF2 ? 3 : 1][Q];
       if constexpr (PF2)
       {
          load_row(0, ra[0]);
          load_row(1, ra[1]);
       }
-      else if constexpr (!W3) { load_row(0, ca); }
+      else { load_row(0, ca); }
       if (RM == 3) { regf = 2; }  // every block lattice-map: no treg row in the gather's chain
       else if (RM)
       {
@@ -504,7 +486,7 @@ k_apply_tpe_sf(int ne, int blk_begin, int blk_end, int n_owned, const int *__res
                for (int dz = 0; dz < D; dz++)
                {
                   const int a = (dz * D + dy) * D + dx;
-                  const double c = a < XL ? sX[w][a][ll] : xl;
+                  const double c = sX[w][a][ll];
                   zb += bz[dz] * c;
                   zg += gz[dz] * c;
                }
@@ -608,20 +590,9 @@ k_apply_tpe_sf(int ne, int blk_begin, int blk_end, int n_owned, const int *__res
 #pragma unroll
                for (int dx = 0; dx < D; dx++)
                {
-                  if constexpr (W3)
-                  {
-                     // no plane sums (36 VGPRs): the row's y-transpose goes straight through the
-                     // z-transpose into the outputs (54 more FMAs per row)
-                     const double pb = by * T0[dx] + gy * T1[dx], pg = by * T2[dx];
-#pragma unroll
-                     for (int dz = 0; dz < D; dz++) { Yo[(dz * D + dy) * D + dx] += bz[dz] * pb + gz[dz] * pg; }
-                  }
-                  else
-                  {
-                     SB[dy][dx] += by * T0[dx];
-                     SB[dy][dx] += gy * T1[dx];
-                     SG[dy][dx] += by * T2[dx];
-                  }
+                  SB[dy][dx] += by * T0[dx];
+                  SB[dy][dx] += gy * T1[dx];
+                  SG[dy][dx] += by * T2[dx];
                }
             }
          };
@@ -635,16 +606,6 @@ k_apply_tpe_sf(int ne, int blk_begin, int blk_end, int n_owned, const int *__res
                __builtin_amdgcn_sched_barrier(0);  // rows stay in program order (no interleaving)
                load_row(row + 2 < NR ? row + 2 : NR - 1, ra[(row + 2) % 3]);
                row_body(qy, ra[row % 3]);
-            }
-         }
-         else if constexpr (W3)
-         {
-            // one row buffer, no prefetch: the third wave per SIMD hides the row's latency
-#pragma unroll
-            for (int qy = 0; qy < Q; qy++)
-            {
-               load_row(qz * Q + qy, ca);
-               row_body(qy, ca);
             }
          }
          else if constexpr (Q % 2 == 0)
@@ -676,7 +637,7 @@ k_apply_tpe_sf(int ne, int blk_begin, int blk_end, int n_owned, const int *__res
             }
          }
 #pragma unroll
-         for (int dz = 0; dz < D && !W3; dz++)
+         for (int dz = 0; dz < D; dz++)
 #pragma unroll
             for (int dy = 0; dy < D; dy++)
 #pragma unroll
@@ -697,7 +658,7 @@ k_apply_tpe_sf(int ne, int blk_begin, int blk_end, int n_owned, const int *__res
          for (int qz = 0; qz < Q; qz++) { plane(qz); }
       }
    }  // wave_on
-   tpe_assemble_store<D, SPLIT, RM == 0 || RM == 2, true, RM != 0, XR, W3>(Yo, mp, wave_on ? lane_flags[(size_t)blk * 64 + lane] : 0,
+   tpe_assemble_store<D, SPLIT, RM == 0 || RM == 2, true, RM != 0, XR>(Yo, mp, wave_on ? lane_flags[(size_t)blk * 64 + lane] : 0,
                                                          blk, lane, active, n_owned, y, yg, part, &sX[0][0][0], w,
                                                          wave_on, rg, regf, pstride,
                                                          lmap ? lmap + (size_t)blk * tpe_lattice_points(D) : nullptr);
@@ -1106,7 +1067,7 @@ k_apply_tpe_tlb(int ne, int blk_begin, int blk_end, int n_owned, const int *__re
 }
 
 // AFFINE apply with the diffusion coefficient evaluated from a snapshot of its temperature field
-// (TS: ApplyArgs::tsnap).  In the bioheat form beta = k(T) is a law of T, an H1 grid function on the
+// (TS: TpeArgs::tsnap).  In the bioheat form beta = k(T) is a law of T, an H1 grid function on the
 // form's own space (GridFunctionCoefficient, coefficient.cpp:250-253, possibly composed with a law as
 // TransformedCoefficient::Eval does, coefficient.cpp:262): the reference evaluates it at the
 // quadrature points at Assemble (CoefficientVector::Project, coefficient.cpp:2052-2070, then
@@ -1677,7 +1638,7 @@ k_diag_tpe(int ne, int blk_begin, int blk_end, int n_owned, const int *__restric
 }
 
 template <int D, int Q, bool MASS, bool DIFF, bool SPLIT>
-void launch_tpe(const ApplyArgs &a, const Basis1D &b, const double *rowtab, hipStream_t s)
+void launch_tpe(const ApplyArgs &a, const TpeArgs &t, const Basis1D &b, const double *rowtab, hipStream_t s)
 {
    const int nb = a.blk_end - a.blk_begin;
    const dim3 grid((nb + 3) / 4), block(256);
@@ -1690,50 +1651,45 @@ void launch_tpe(const ApplyArgs &a, const Basis1D &b, const double *rowtab, hipS
          ECM2_VERIFY(a.pw == PW, ERR_INTERNAL, "TRILINEAR point values do not match the integrators");
 #define ECM2_TL(KT)                                                                                           \
    hipLaunchKernelGGL(KT, grid, block, 0, s, a.ne, a.blk_begin, a.blk_end, a.n_owned, a.gmap, a.qdd, a.qdm, a.x, \
-                      a.xg, a.y, a.yg, b, a.lane_flags, a.part, a.treg, a.part_stride, a.lmap, a.qp)
+                      a.xg, a.y, a.yg, b, t.lane_flags, a.part, t.treg, t.part_stride, t.lmap, a.qp)
          // every block a lattice brick: the two-waves-per-SIMD lattice kernel; else per element
          // (p = 2; at p = 1 the per-element kernel fits two waves already)
 #define ECM2_TLB(RM)                                                                                          \
    hipLaunchKernelGGL((k_apply_tpe_tlb<3, 4, SPLIT, RM, PW>), grid, block, 0, s, a.ne, a.blk_begin, a.blk_end,      \
-                      a.n_owned, a.gmap, a.qdd, a.qdm, a.x, a.xg, a.y, a.yg, b, a.lane_flags, a.part, a.treg,      \
-                      a.part_stride, a.lmap, a.qp)
+                      a.n_owned, a.gmap, a.qdd, a.qdm, a.x, a.xg, a.y, a.yg, b, t.lane_flags, a.part, t.treg,      \
+                      t.part_stride, t.lmap, a.qp)
          constexpr bool LAT = D == 3 && Q == 4;
-         if (LAT && a.treg && a.treg_all) { ECM2_TLB(1); }
-         else if (LAT && a.treg && a.tlat_all) { ECM2_TLB(3); }
+         if (LAT && t.treg && t.treg_all) { ECM2_TLB(1); }
+         else if (LAT && t.treg && t.tlat_all) { ECM2_TLB(3); }
 #undef ECM2_TLB
-         else if (a.treg) { ECM2_TL((k_apply_tpe_sf<D, Q, SPLIT, 2, true, PW>)); }
+         else if (t.treg) { ECM2_TL((k_apply_tpe_sf<D, Q, SPLIT, 2, true, PW>)); }
          else { ECM2_TL((k_apply_tpe_sf<D, Q, SPLIT, 0, true, PW>)); }
 #undef ECM2_TL
       }
       else { ECM2_VERIFY(false, ERR_INTERNAL, "TRILINEAR qdata needs the diffusion integrator"); }
       return;
    }
-   if (a.kind == QLAYOUT_AFFINE && a.tsnap)
+   if (a.kind == QLAYOUT_AFFINE && t.tsnap)
    {
       // the diffusion coefficient from its field snapshot: W alpha det J per point (tmass 1), or no
       // per-point stream (tmass 2)
       if constexpr (DIFF && D == 3 && Q == 4)
       {
-         ECM2_VERIFY(a.tmass == (MASS ? a.tmass : 0) && (a.tmass != 0) == MASS && a.pw == (a.tmass == 1 ? 1 : 0) &&
-                        a.treg && (a.treg_all || a.tlat_all) && a.tsnap_kind == (a.treg_all ? 1 : 2),
+         ECM2_VERIFY(t.tmass == (MASS ? t.tmass : 0) && (t.tmass != 0) == MASS && a.pw == (t.tmass == 1 ? 1 : 0) &&
+                        t.treg && (t.treg_all || t.tlat_all) && t.tsnap_kind == (t.treg_all ? 1 : 2),
                      ERR_INTERNAL, "coefficient snapshot needs lattice blocks and matching mass values");
-         Basis1D bw = b;  // (w B): the weight-scaled interpolation of T' (LAW = false)
-         for (int d = 0; d < MAX_D1D; d++)
-            for (int q = 0; q < MAX_Q1D; q++) { bw.B[q + MQ * d] = a.qw[q] * b.B[q + MQ * d]; }
-         QPts qw = {};
-         for (int q = 0; q < MAX_Q1D; q++) { qw.x[q] = a.qw[q]; }
 #define ECM2_TS(RM, MM, LAW, CD)                                                                                    \
    hipLaunchKernelGGL((k_apply_tpe_ts<3, 4, SPLIT, RM, MM, LAW, CD>), grid, block, 0, s, a.ne, a.blk_begin, a.blk_end, \
-                      a.n_owned, a.gmap, a.qdd, a.qdm, a.x, a.xg, a.tsnap, a.y, a.yg, b, bw, a.lane_flags, a.part,     \
-                      a.treg, a.part_stride, a.lmap, qw, a.law_d, a.law_m, a.en)
+                      a.n_owned, a.gmap, a.qdd, a.qdm, a.x, a.xg, t.tsnap, a.y, a.yg, b, t.bw, t.lane_flags, a.part,   \
+                      t.treg, t.part_stride, t.lmap, t.qw, t.law_d, t.law_m, a.en)
 #define ECM2_TS_MM(RM, LAW, CD)                                                                                     \
    if (!MASS) { ECM2_TS(RM, 0, LAW, CD); }                                                                          \
-   else if (a.tmass == 1) { ECM2_TS(RM, 1, LAW, CD); }                                                              \
+   else if (t.tmass == 1) { ECM2_TS(RM, 1, LAW, CD); }                                                              \
    else { ECM2_TS(RM, 2, LAW, CD); }
 #define ECM2_TS_LAW(RM, CD)                                                                                         \
-   if (a.tlaw) { ECM2_TS_MM(RM, true, CD) } else { ECM2_TS_MM(RM, false, CD) }
+   if (t.tlaw) { ECM2_TS_MM(RM, true, CD) } else { ECM2_TS_MM(RM, false, CD) }
          // (axis-aligned meshes: the diagonal flux product, a.cdiag)
-         if (a.treg_all)
+         if (t.treg_all)
          {
             if (a.cdiag) { ECM2_TS_LAW(1, true) } else { ECM2_TS_LAW(1, false) }
          }
@@ -1756,18 +1712,18 @@ void launch_tpe(const ApplyArgs &a, const Basis1D &b, const double *rowtab, hipS
          if (MASS && a.latency)
          {
             hipLaunchKernelGGL((k_apply_tpe_pp<D, Q, SPLIT>), dim3(nb), dim3(256), 0, s, a.ne, a.blk_begin,
-                               a.n_owned, a.gmap, a.qdd, a.qdm, a.x, a.xg, a.y, a.yg, b, a.lane_flags, a.part,
-                               a.part_stride);
+                               a.n_owned, a.gmap, a.qdd, a.qdm, a.x, a.xg, a.y, a.yg, b, t.lane_flags, a.part,
+                               t.part_stride);
          }
          else
          {
 #define ECM2_SF(RM)                                                                                           \
    hipLaunchKernelGGL((k_apply_tpe_sf<D, Q, SPLIT, RM, false, PW>), grid, block, 0, s, a.ne, a.blk_begin, a.blk_end, \
-                      a.n_owned, a.gmap, a.qdd, a.qdm, a.x, a.xg, a.y, a.yg, b, a.lane_flags, a.part, a.treg,       \
-                      a.part_stride, a.lmap, a.qp)
-            if (a.treg && a.treg_all) { ECM2_SF(1); }
-            else if (a.treg && a.tlat_all) { ECM2_SF(3); }
-            else if (a.treg) { ECM2_SF(2); }
+                      a.n_owned, a.gmap, a.qdd, a.qdm, a.x, a.xg, a.y, a.yg, b, t.lane_flags, a.part, t.treg,       \
+                      t.part_stride, t.lmap, a.qp)
+            if (t.treg && t.treg_all) { ECM2_SF(1); }
+            else if (t.treg && t.tlat_all) { ECM2_SF(3); }
+            else if (t.treg) { ECM2_SF(2); }
             else { ECM2_SF(0); }
 #undef ECM2_SF
          }
@@ -1776,39 +1732,40 @@ void launch_tpe(const ApplyArgs &a, const Basis1D &b, const double *rowtab, hipS
       return;
    }
    hipLaunchKernelGGL((k_apply_tpe_pf<D, Q, MASS, DIFF, SPLIT>), grid, block, 0, s, a.ne, a.blk_begin, a.blk_end,
-                      a.n_owned, a.gmap, a.qdd, a.qdm, a.x, a.xg, a.y, a.yg, b, rowtab, a.lane_flags, a.part);
+                      a.n_owned, a.gmap, a.qdd, a.qdm, a.x, a.xg, a.y, a.yg, b, rowtab, t.lane_flags, a.part);
 }
 
 template <int D, int Q, bool MASS, bool DIFF>
-void launch_tpe_mdq(const ApplyArgs &a, const Basis1D &b, const double *rowtab, hipStream_t s)
+void launch_tpe_mdq(const ApplyArgs &a, const TpeArgs &t, const Basis1D &b, const double *rowtab, hipStream_t s)
 {
    if (a.blk_end <= a.blk_begin) { return; }
-   ECM2_VERIFY(a.lane_flags, ERR_INTERNAL, "thread-per-element kernel needs the merge plan");
-   if (a.xg || a.yg) { launch_tpe<D, Q, MASS, DIFF, true>(a, b, rowtab, s); }
-   else { launch_tpe<D, Q, MASS, DIFF, false>(a, b, rowtab, s); }
+   ECM2_VERIFY(t.lane_flags, ERR_INTERNAL, "thread-per-element kernel needs the merge plan");
+   if (a.xg || a.yg) { launch_tpe<D, Q, MASS, DIFF, true>(a, t, b, rowtab, s); }
+   else { launch_tpe<D, Q, MASS, DIFF, false>(a, t, b, rowtab, s); }
 }
 
 template <int D, int Q>
-void launch_tpe_dq(bool mass, bool diff, const ApplyArgs &a, const Basis1D &b, const double *rowtab, hipStream_t s)
+void launch_tpe_dq(bool mass, bool diff, const ApplyArgs &a, const TpeArgs &t, const Basis1D &b, const double *rowtab,
+                   hipStream_t s)
 {
-   if (mass && diff) { launch_tpe_mdq<D, Q, true, true>(a, b, rowtab, s); }
-   else if (mass) { launch_tpe_mdq<D, Q, true, false>(a, b, rowtab, s); }
-   else if (diff) { launch_tpe_mdq<D, Q, false, true>(a, b, rowtab, s); }
+   if (mass && diff) { launch_tpe_mdq<D, Q, true, true>(a, t, b, rowtab, s); }
+   else if (mass) { launch_tpe_mdq<D, Q, true, false>(a, t, b, rowtab, s); }
+   else if (diff) { launch_tpe_mdq<D, Q, false, true>(a, t, b, rowtab, s); }
 }
 
 template <int D, int Q, bool MASS, bool DIFF>
-void launch_diag_tpe(const ApplyArgs &a, const Basis1D &b, const double *drow, hipStream_t s)
+void launch_diag_tpe(const ApplyArgs &a, const TpeArgs &t, const Basis1D &b, const double *drow, hipStream_t s)
 {
    const int nb = a.blk_end - a.blk_begin;
    if (nb <= 0) { return; }
    const dim3 grid((nb + 3) / 4), block(256);
 #define ECM2_DIAG(SP, AF, XV)                                                                            \
    hipLaunchKernelGGL((k_diag_tpe<D, Q, MASS, DIFF, SP, AF, XV>), grid, block, 0, s, a.ne, a.blk_begin,        \
-                      a.blk_end, a.n_owned, a.gmap, a.qdd, a.qdm, a.y, a.yg, b, drow, a.lane_flags, a.part,  \
-                      XV ? a.treg : nullptr, a.part_stride, XV ? a.lmap : nullptr)
+                      a.blk_end, a.n_owned, a.gmap, a.qdd, a.qdm, a.y, a.yg, b, drow, t.lane_flags, a.part,  \
+                      XV ? t.treg : nullptr, t.part_stride, XV ? t.lmap : nullptr)
    const bool aff = a.kind == QLAYOUT_AFFINE;
-   // a.xwave: the plan was built with cross-wave faces (AFFINE or TRILINEAR forms)
-   const bool xw = aff || a.xwave;
+   // t.xwave: the plan was built with cross-wave faces (AFFINE or TRILINEAR forms)
+   const bool xw = aff || t.xwave;
    ECM2_VERIFY(!aff || (MASS && DIFF), ERR_INTERNAL, "AFFINE qdata needs both integrators");
    if (a.yg)
    {
@@ -1826,12 +1783,12 @@ void launch_diag_tpe(const ApplyArgs &a, const Basis1D &b, const double *drow, h
 }
 
 template <int D, int Q>
-void launch_diag_tpe_dq(bool mass, bool diff, const ApplyArgs &a, const Basis1D &b, const double *drow,
-                        hipStream_t s)
+void launch_diag_tpe_dq(bool mass, bool diff, const ApplyArgs &a, const TpeArgs &t, const Basis1D &b,
+                        const double *drow, hipStream_t s)
 {
-   if (mass && diff) { launch_diag_tpe<D, Q, true, true>(a, b, drow, s); }
-   else if (mass) { launch_diag_tpe<D, Q, true, false>(a, b, drow, s); }
-   else if (diff) { launch_diag_tpe<D, Q, false, true>(a, b, drow, s); }
+   if (mass && diff) { launch_diag_tpe<D, Q, true, true>(a, t, b, drow, s); }
+   else if (mass) { launch_diag_tpe<D, Q, true, false>(a, t, b, drow, s); }
+   else if (diff) { launch_diag_tpe<D, Q, false, true>(a, t, b, drow, s); }
 }
 
 } // namespace
@@ -1839,22 +1796,22 @@ void launch_diag_tpe_dq(bool mass, bool diff, const ApplyArgs &a, const Basis1D 
 namespace kern
 {
 
-void apply_tpe(int D, int Q, bool mass, bool diff, const ApplyArgs &a, const Basis1D &b,
+void apply_tpe(int D, int Q, bool mass, bool diff, const ApplyArgs &a, const TpeArgs &t, const Basis1D &b,
                const double *rowtab, hipStream_t s)
 {
    if (a.ne == 0) { return; }
-   if (D == 2 && Q == 3) { launch_tpe_dq<2, 3>(mass, diff, a, b, rowtab, s); }
-   else if (D == 3 && Q == 4) { launch_tpe_dq<3, 4>(mass, diff, a, b, rowtab, s); }
+   if (D == 2 && Q == 3) { launch_tpe_dq<2, 3>(mass, diff, a, t, b, rowtab, s); }
+   else if (D == 3 && Q == 4) { launch_tpe_dq<3, 4>(mass, diff, a, t, b, rowtab, s); }
    else { ECM2_VERIFY(false, ERR_UNSUPPORTED, "no thread-per-element kernel for D1D=" << D << " Q1D=" << Q); }
    ECM2_HIP(hipGetLastError());
 }
 
-void diagonal_tpe(int D, int Q, bool mass, bool diff, const ApplyArgs &a, const Basis1D &b, const double *drow,
-                  hipStream_t s)
+void diagonal_tpe(int D, int Q, bool mass, bool diff, const ApplyArgs &a, const TpeArgs &t, const Basis1D &b,
+                  const double *drow, hipStream_t s)
 {
    if (a.ne == 0) { return; }
-   if (D == 2 && Q == 3) { launch_diag_tpe_dq<2, 3>(mass, diff, a, b, drow, s); }
-   else if (D == 3 && Q == 4) { launch_diag_tpe_dq<3, 4>(mass, diff, a, b, drow, s); }
+   if (D == 2 && Q == 3) { launch_diag_tpe_dq<2, 3>(mass, diff, a, t, b, drow, s); }
+   else if (D == 3 && Q == 4) { launch_diag_tpe_dq<3, 4>(mass, diff, a, t, b, drow, s); }
    else { ECM2_VERIFY(false, ERR_UNSUPPORTED, "no thread-per-element diagonal for D1D=" << D << " Q1D=" << Q); }
    ECM2_HIP(hipGetLastError());
 }

@@ -72,7 +72,7 @@ struct QLayout
    int pw = 2;
    // AFFINE (p = 2, lattice blocks) with the diffusion coefficient a law of an H1 field on the form's
    // space (grid-function coefficient kinds): the kernel interpolates a snapshot of the field
-   // (ApplyArgs::tsnap) instead of reading W beta per point.
+   // (TpeArgs::tsnap) instead of reading W beta per point.
    // 1: the snapshot in dof order (regular blocks); 2: in the lattice-map blocks' slot order
    int tsnap = 0;
    // with tsnap, the mass: 0 none; 1 W alpha det J per point (pw = 1: a quadrature coefficient, or a
@@ -210,47 +210,59 @@ __host__ __device__ inline double point_law(const PointLaw &l, double T)
 }
 
 // Arguments of one fused apply over element blocks [blk_begin, blk_end) (64 elements per
-// block).  With a split L-vector (distributed form) dofs >= n_owned live in xg / yg.
+// block): what varies per call or is common to the three kernel families.  With a split L-vector
+// (distributed form) dofs >= n_owned live in xg / yg.
 struct ApplyArgs
 {
    int kind = QLAYOUT_NATIVE;
    int pw = 2;                      // AFFINE / TRILINEAR point values (QLayout::pw)
    int ne = 0, blk_begin = 0, blk_end = 0, n_owned = 0;
    const int *pos = nullptr;        // element permutation (blocked layout), may be null
-   const int *lane_flags = nullptr; // [blk][64]: in-wave face merge flags
-   const int *treg = nullptr;       // device [blk][8]: 4x4x4 blocks (base, sx, sy, sz, face mask, -, -, flag: 1 regular, 2 lattice slots), or null
-   int treg_all = 0;                // every block regular
-   int tlat_all = 0;                // every block a lattice-map block (treg flag 2)
-   int part_stride = 0;             // p <= 2 partial slots per block (27 * 64, or the lattice surface when treg_all)
-   const int *lmap = nullptr;       // device [blk][tpe_lattice_points]: lattice-slot blocks' lattice maps, or null
-   QPts qp = {};                    // TRILINEAR: the quadrature points
-   // AFFINE with a coefficient snapshot (QLayout::tsnap): T' = A + B T at the form's L-vector dofs
-   // (the diffusion coefficient's law applied to its field at Assemble) and the 1D Gauss weights
-   const double *tsnap = nullptr;
-   int tsnap_kind = 0;              // QLayout::tsnap
-   int tmass = 0, tlaw = 0;         // QLayout::tmass, QLayout::tlaw
-   int cdiag = 0;                   // snapshot forms: every element's C = adj(J) adj(J)^T / det J diagonal
-   PointLaw law_d, law_m;           // tlaw = 1: the diffusion and mass laws at the point
-   double qw[MAX_Q1D] = {};
-   int xwave = 0;                   // the merge plan has cross-wave faces (AFFINE / TRILINEAR forms)
    const int *gmap = nullptr;
    const double *qdd = nullptr, *qdm = nullptr;
    const double *x = nullptr, *xg = nullptr;
    double *y = nullptr, *yg = nullptr;
    double *part = nullptr;          // partial slots of shared dofs (null: atomics)
+   QPts qp = {};                    // TRILINEAR: the quadrature points
+   int cdiag = 0;                   // snapshot forms: every element's C = adj(J) adj(J)^T / det J diagonal
    bool latency = false;            // TPE + AFFINE: one workgroup per block, a plane per wave (small ranges)
-   const Basis1D *btab = nullptr;   // LINE / brick / diagonal: device copy of the (D1D, Q1D) tables
-   const int *lelem = nullptr;      // LINE: device list of the elements outside bricks
-   const int *lelem_off = nullptr;  // LINE: host [nblk + 1], listed elements of 64-element block b
-   // LINE, brick part (p >= 3 on structured regions): bricks of 2 x 2 x brick_bz elements
+   // k_apply_tpe_ts: the Mult's energy x^T A x as one partial per workgroup (en[workgroup]), or null
+   double *en = nullptr;
+};
+
+// The thread-per-element kernels' (p <= 2) plan and snapshot arguments: fixed at Assemble.
+struct TpeArgs
+{
+   const int *lane_flags = nullptr; // [blk][64]: in-wave face merge flags
+   const int *treg = nullptr;       // device [blk][8]: 4x4x4 blocks (base, sx, sy, sz, face mask, -, -, flag: 1 regular, 2 lattice slots), or null
+   int treg_all = 0;                // every block regular
+   int tlat_all = 0;                // every block a lattice-map block (treg flag 2)
+   int part_stride = 0;             // partial slots per block (27 * 64, or the lattice surface when treg_all)
+   const int *lmap = nullptr;       // device [blk][tpe_lattice_points]: lattice-slot blocks' lattice maps, or null
+   int xwave = 0;                   // the merge plan has cross-wave faces (AFFINE / TRILINEAR forms)
+   // AFFINE with a coefficient snapshot (QLayout::tsnap): T' = A + B T at the form's L-vector dofs
+   // (the diffusion coefficient's law applied to its field at Assemble)
+   const double *tsnap = nullptr;
+   int tsnap_kind = 0;              // QLayout::tsnap
+   int tmass = 0, tlaw = 0;         // QLayout::tmass, QLayout::tlaw
+   PointLaw law_d, law_m;           // tlaw = 1: the diffusion and mass laws at the point
+   QPts qw = {};                    // the 1D Gauss weights
+   Basis1D bw = {};                 // (w B): the weight-scaled interpolation of T' (tlaw = 0)
+};
+
+// The line kernel family's (p >= 3) plan arguments: fixed at Assemble.
+struct LineArgs
+{
+   const Basis1D *btab = nullptr;   // device copy of the (D1D, Q1D) tables
+   const int *lelem = nullptr;      // device list of the elements outside bricks
+   const int *lelem_off = nullptr;  // host [nblk + 1], listed elements of 64-element block b
+   // brick part (p >= 3 on structured regions): bricks of 2 x 2 x brick_bz elements
    const int *belem = nullptr;      // device [nbrick][4 bz] element ids (qdata addressing)
    const int *bmap = nullptr;       // device [nbrick][NB] lattice map: dof | shared << 30
    const int *breg = nullptr;       // device [nbrick][8]: regular bricks (base, sx, sy, sz, face mask), or null
    const int *brick_off = nullptr;  // host [nblk + 1], bricks whose first element lies in block b
    int brick_bz = 0;                // 0: no bricks
    double *part_brick = nullptr;    // partial slots [nbrick][surface] of shared lattice points
-   // k_apply_tpe_ts: the Mult's energy x^T A x as one partial per workgroup (en[workgroup]), or null
-   double *en = nullptr;
 };
 
 // Partial-slot order of a brick's surface lattice points (2 x 2 x bz elements, lattice
@@ -274,34 +286,15 @@ __host__ __device__ constexpr int lattice_surface_index(int LX, int LY, int LZ, 
    if (X == LX - 1) { return b2 + (LZ - 2) * (LY - 2) + (Z - 1) * (LY - 2) + (Y - 1); }
    return -1;
 }
-// Brick partial slots: the same face groups, each group starting on a multiple of kBrickSlotAlign
-// doubles (ECM2_BRICK_SLOT_ALIGN, an A/B build: 16 = every group on its own 128-B lines).
-#ifndef ECM2_BRICK_SLOT_ALIGN
-#define ECM2_BRICK_SLOT_ALIGN 1
-#endif
-constexpr int kBrickSlotAlign = ECM2_BRICK_SLOT_ALIGN;
-__host__ __device__ constexpr int slot_align_up(int n) { return (n + kBrickSlotAlign - 1) / kBrickSlotAlign * kBrickSlotAlign; }
+// a brick's slots: the lattice's face-grouped order
 __host__ __device__ constexpr int brick_surface_points(int D, int bz)
 {
-   const int LX = 2 * D - 1, LY = LX, LZ = bz * (D - 1) + 1;
-   return 2 * slot_align_up(LX * LY) + 2 * slot_align_up((LZ - 2) * LX) + 2 * slot_align_up((LZ - 2) * (LY - 2));
+   return lattice_surface_points(2 * D - 1, 2 * D - 1, bz * (D - 1) + 1);
 }
 __host__ __device__ constexpr int brick_surface_index(int D, int bz, int X, int Y, int Z)
 {
-   const int LX = 2 * D - 1, LY = LX, LZ = bz * (D - 1) + 1;
-   const int gz = slot_align_up(LX * LY), gy = slot_align_up((LZ - 2) * LX), gx = slot_align_up((LZ - 2) * (LY - 2));
-   if (Z == 0) { return Y * LX + X; }
-   if (Z == LZ - 1) { return gz + Y * LX + X; }
-   if (Y == 0) { return 2 * gz + (Z - 1) * LX + X; }
-   if (Y == LY - 1) { return 2 * gz + gy + (Z - 1) * LX + X; }
-   if (X == 0) { return 2 * gz + 2 * gy + (Z - 1) * (LY - 2) + (Y - 1); }
-   if (X == LX - 1) { return 2 * gz + 2 * gy + gx + (Z - 1) * (LY - 2) + (Y - 1); }
-   return -1;
+   return lattice_surface_index(2 * D - 1, 2 * D - 1, bz * (D - 1) + 1, X, Y, Z);
 }
-static_assert(kBrickSlotAlign != 1 || (brick_surface_points(5, 1) == lattice_surface_points(9, 9, 5) &&
-                                       brick_surface_index(5, 1, 3, 4, 2) == lattice_surface_index(9, 9, 5, 3, 4, 2) &&
-                                       brick_surface_index(5, 1, 8, 4, 2) == lattice_surface_index(9, 9, 5, 8, 4, 2)),
-              "unaligned brick slots are the lattice's face-grouped order");
 // the same for a p <= 2 block (4 x 4 x 4 elements, lattice 4 (D-1) + 1 per side)
 __host__ __device__ inline int tpe_surface_points(int D)
 {
@@ -459,16 +452,16 @@ void setup_from_jacobians(const QLayout &L, const double *J, const double *W,
 
 // ---- apply ----
 // Fused y = R^T (M + K) R x, thread-per-element (blocked layout); y must be zeroed.
-void apply_tpe(int D, int Q, bool mass, bool diff, const ApplyArgs &a, const Basis1D &b,
+void apply_tpe(int D, int Q, bool mass, bool diff, const ApplyArgs &a, const TpeArgs &t, const Basis1D &b,
                const double *rowtab, hipStream_t s);
 // Row table for apply_tpe: [qz][qy][3][dz][dy] products (see k_tpe.hip).
 std::vector<double> make_row_table(const DofToQuad &m);
-// Line kernel: one wave per listed element (a.lelem), native or AFFINE_E qdata, L-vectors
+// Line kernel: one wave per listed element (l.lelem), native or AFFINE_E qdata, L-vectors
 // through an encoded map [e][nd] (dof | shared << 30 | sign << 31); shared dofs go to
-// part[e*nd + a] when a.part is set, else atomics; then the bricks (a.brick_bz).
+// part[e*nd + a] when a.part is set, else atomics; then the bricks (l.brick_bz).
 // has_line: (D, Q) instantiated.
 bool has_line(int D, int Q);
-void apply_line(int D, int Q, bool mass, bool diff, const ApplyArgs &a, hipStream_t s);
+void apply_line(int D, int Q, bool mass, bool diff, const ApplyArgs &a, const LineArgs &l, hipStream_t s);
 // Brick kernel of the line family: (D, Q, bz) instantiated?  Lattice points per brick.
 bool has_brick(int D, int Q, int bz);
 int brick_points(int D, int bz);
@@ -509,9 +502,9 @@ void restriction_mult_transpose(int ndofs, int nd, const int *offsets, const int
 
 // ---- diagonal (Jacobi) ----
 // Thread-per-element diagonal on the blocked layout, assembled/stored like apply_tpe (a.y /
-// a.yg / a.part / a.lane_flags; a.x unused); drow = make_diag_row_table.
-void diagonal_tpe(int D, int Q, bool mass, bool diff, const ApplyArgs &a, const Basis1D &b, const double *drow,
-                  hipStream_t s);
+// a.yg / a.part / t.lane_flags; a.x unused); drow = make_diag_row_table.
+void diagonal_tpe(int D, int Q, bool mass, bool diff, const ApplyArgs &a, const TpeArgs &t, const Basis1D &b,
+                  const double *drow, hipStream_t s);
 std::vector<double> make_diag_row_table(const DofToQuad &m);
 // Sum-factorised workgroup-per-element diagonal, any layout; L-vector (atomics) or E-vector.
 void diagonal(const int *pos, int D, int Q, int layout, int ne, const int *gmap_native, const double *qd_diff,

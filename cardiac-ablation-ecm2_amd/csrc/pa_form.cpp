@@ -1,9 +1,8 @@
 // pa_form.cpp -- see pa_form.hpp.  The device side of a form: geometry, qdata, uploads and kernel
 // launches.  What the fused kernels' deterministic scatter needs (element order, merge flags, maps,
 // lattice units, partial slots, the summation plan) is planned on the host in scatter_plan.cpp;
-// plan_tpe / plan_line below call it and upload the result.
+// plan_tpe / plan_line below call it and hand the result to the plan objects (plan_dev.hpp).
 #include "pa_form.hpp"
-#include "scatter_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -38,6 +37,7 @@ PAForm::PAForm(int ne, int order, int ndofs, const int *gather_map_host, int q1d
    maps_ = make_dof_to_quad(order, Q_);
    basis_ = make_basis1d(maps_);
    basis1_ = make_basis1d(make_dof_to_quad(1, Q_));
+   for (int q = 0; q < Q_; q++) { qp_.x[q] = maps_.qpts[q]; }
    gmap_host_.assign(gather_map_host, gather_map_host + (size_t)ne * ND_);
    for (int g : gmap_host_)
    {
@@ -113,20 +113,15 @@ void PAForm::set_block_splits(const std::vector<int> &splits)
 {
    for (int b : splits) { ECM2_VERIFY(b >= 0 && b <= layout_.nblk(), ERR_ARG, "block split " << b << " out of range"); }
    splits_ = splits;
-   gmap_line_.resize(0);
-   if (perm_auto_)  // the derived brick order respects the segments: derive it again
-   {
-      perm_host_.clear();
-      perm_auto_ = false;
-      gmap_blk_.resize(0);
-   }
+   // (the derived element order, the workgroup groups of the merge plan and the bricks respect the segments)
+   invalidate_plans(true, true);
    assembled_ = false;
 }
 
 void PAForm::set_latency_from(int b)
 {
    latency_from_ = b;
-   gmap_blk_.resize(0);  // the face-assembly plan depends on it: rebuild
+   invalidate_plans(true, false);  // the face-assembly plan depends on it
    assembled_ = false;
 }
 
@@ -134,7 +129,7 @@ void PAForm::set_line_bricks(int bz)
 {
    ECM2_VERIFY(bz >= -1 && bz <= 2, ERR_ARG, "brick mode " << bz << " not in {-1, 0, 1, 2}");
    line_bricks_ = bz;
-   gmap_line_.resize(0);
+   invalidate_plans(false, true);
    assembled_ = false;
 }
 
@@ -171,21 +166,20 @@ void PAForm::add_integrator(int kind, const CoeffDesc &c, const int *marker, int
    marked_[kind] = marker != nullptr;
    marker_[kind].assign(marker, marker ? marker + n_marker : marker);
    order_added_.push_back(kind);
+   invalidate_plans(false, true);  // bricks need both integrators
    assembled_ = false;
 }
 
 void PAForm::set_element_order(const int *perm)
 {
    std::vector<int> seen(ne_, 0);
-   perm_host_.assign(perm, perm + ne_);
-   perm_auto_ = false;
-   for (int e : perm_host_)
+   user_perm_.assign(perm, perm + ne_);
+   for (int e : user_perm_)
    {
       ECM2_VERIFY(e >= 0 && e < ne_ && !seen[e], ERR_ARG, "element order is not a permutation");
       seen[e] = 1;
    }
-   gmap_blk_.resize(0);
-   gmap_line_.resize(0);
+   invalidate_plans(true, false);
    assembled_ = false;
 }
 
@@ -193,9 +187,14 @@ void PAForm::set_kernel(int mode)
 {
    ECM2_VERIFY(mode >= KERNEL_AUTO && mode <= KERNEL_LINE, ERR_ARG, "unknown kernel mode " << mode);
    mode_ = mode;
-   gmap_blk_.resize(0);   // the scatter plan belongs to one fused kernel: rebuild it
-   gmap_line_.resize(0);
+   invalidate_plans(true, true);  // the summation plan belongs to one fused kernel
    assembled_ = false;
+}
+
+void PAForm::invalidate_plans(bool tpe, bool line)
+{
+   if (tpe) { tpe_.reset(); }
+   if (line) { line_.reset(); }
 }
 
 static bool has_tpe(int D, int Q) { return (D == 2 && Q == 3) || (D == 3 && Q == 4); }
@@ -213,18 +212,19 @@ void PAForm::assemble(hipStream_t s)
       btab_.upload(&bd, 1, s);
    }
    plan_line(s);
-   layout_.pos = layout_.blocked() ? pos_.data() : nullptr;
-   layout_.perm = layout_.blocked() ? perm_dev_.data() : nullptr;
+   layout_.pos = layout_.blocked() ? tpe_.pos.data() : nullptr;
+   layout_.perm = layout_.blocked() ? tpe_.perm_dev.data() : nullptr;
    if (!use_partials()) { part_.resize(0); }
    else if (resolved_mode_ == KERNEL_LINE)
    {
       // [bricks' lattice slots | leftover elements' [e][nd] slots (when there are any)]
-      part_.resize(std::max<size_t>(1, (size_t)part_line_off_ + (n_left_ ? (size_t)ne_ * ND_ : 0)));
+      part_.resize(std::max<size_t>(1, (size_t)line_.info.part_line_off + (line_.info.n_left ? (size_t)ne_ * ND_ : 0)));
    }
-   else { part_.resize((size_t)layout_.nblk() * part_stride_); }
+   else { part_.resize((size_t)layout_.nblk() * tpe_.info.part_stride); }
    choose_snapshot(s);
    setup_qdata(s);
    setup_marker_diagonal(s);
+   build_launch_args();
    assembled_ = true;
    gen_++;
 }
@@ -276,10 +276,8 @@ void PAForm::resolve_layout(hipStream_t s)
       bool tl = !jac_ && enodes_.size();
       if (jac_)
       {
-         QPts qp = {};
-         for (int q = 0; q < Q_ && q < MAX_Q1D; q++) { qp.x[q] = maps_.qpts[q]; }
          cfit_.resize(std::max(1, ne_) * 21);
-         tl = kern::jacobians_trilinear_fit(ne_, Q_, qp, jac_, cfit_.data(), s);
+         tl = kern::jacobians_trilinear_fit(ne_, Q_, qp_, jac_, cfit_.data(), s);
       }
       if (tl)
       {
@@ -289,76 +287,34 @@ void PAForm::resolve_layout(hipStream_t s)
    }
 }
 
-void PAForm::upload_shared_plan(const SharedPlan &p, hipStream_t s)
-{
-   n_sh_ = p.n_sh;
-   n_sh_owned_ = p.n_sh_owned;
-   n_slots_ = p.n_slots;
-   n_runs_ = p.n_runs;
-   n_explicit_runs_ = p.n_explicit_runs;
-   sh_nblk_owned_ = p.nblk_owned;
-   sh_nblk_ = p.nblk;
-   sh_runs_.upload(p.runs, s);
-   sh_rslots_.upload(p.rslots.empty() ? std::vector<int>{0} : p.rslots, s);
-   sh_blocks_.upload(p.blocks.empty() ? std::vector<int>{0, 0, 0, 0} : p.blocks, s);
-   sh_pdof_.upload(p.pdof.empty() ? std::vector<int>{0} : p.pdof, s);
-}
-
 void PAForm::plan_tpe(hipStream_t s)
 {
    // the merge plan (cross-wave faces), the regular blocks and the partial-slot layout belong
    // to the qdata layout they were built for
-   if (gmap_blk_.size() && plan_kind_ != layout_.kind) { gmap_blk_.resize(0); }
-   if (resolved_mode_ != KERNEL_TPE || gmap_blk_.size() || ne_ == 0) { return; }
-   plan_kind_ = layout_.kind;
+   if (tpe_.valid && tpe_.kind != layout_.kind) { invalidate_plans(true, false); }
+   if (resolved_mode_ != KERNEL_TPE || tpe_.valid || ne_ == 0) { return; }
    const bool lattice_layout = layout_.kind == QLAYOUT_AFFINE || layout_.kind == QLAYOUT_TRILINEAR;
-   TpePlan p = build_tpe_plan(ne_, D_, ndofs_, n_owned_, gmap_host_, perm_host_, splits_, latency_from_, lattice_layout,
-                              plan_options_from_env());
-   n_treg_ = p.n_treg;
-   n_tlat_ = p.n_tlat;
-   treg_all_ = p.treg_all;
-   tlat_all_ = p.tlat_all;
-   part_stride_ = p.part_stride;
-   lmap_.upload(p.lmap, s);
-   treg_.upload(p.treg, s);
-   upload_shared_plan(p.shared, s);
-   gmap_blk_.upload(p.gmap_blk, s);
-   lane_flags_.upload(p.lane_flags, s);
-   pos_.upload(p.pos, s);
-   perm_dev_.upload(p.perm, s);
+   const TpePlan p = build_tpe_plan(ne_, D_, ndofs_, n_owned_, gmap_host_, user_perm_, splits_, latency_from_,
+                                    lattice_layout, plan_options_from_env());
+   tpe_.upload(p, layout_.kind, s);
+   shared_.upload(p.shared, s);
    rowtab_.upload(kern::make_row_table(maps_), s);
    drowtab_.upload(kern::make_diag_row_table(maps_), s);
    ECM2_HIP(hipStreamSynchronize(s));  // the uploads read p
-   if (p.perm_derived)
-   {
-      perm_host_ = std::move(p.perm);
-      perm_auto_ = true;
-   }
 }
 
 void PAForm::plan_line(hipStream_t s)
 {
-   if (resolved_mode_ != KERNEL_LINE || gmap_line_.size() || ne_ == 0) { return; }
+   if (resolved_mode_ != KERNEL_LINE || line_.valid || ne_ == 0) { return; }
    // default 2 x 2 x 1 (C5, profiles/ab_brick.sh: 0.861 ms against 1.018 ms per element and
    // 1.114 ms for 2 x 2 x 2)
    int bz = (scatter_ == SCATTER_PARTIALS && have_mass_ && have_diff_) ? (line_bricks_ >= 0 ? line_bricks_ : 1) : 0;
    if (bz == 2 && !kern::has_brick(D_, Q_, 2)) { bz = 1; }
    if (bz == 1 && !kern::has_brick(D_, Q_, 1)) { bz = 0; }
-   LinePlan p = build_line_plan(ne_, D_, ndofs_, n_owned_, gmap_host_, splits_, bz, plan_options_from_env());
-   n_bricks_ = p.n_bricks;
-   brick_bz_ = p.brick_bz;
-   brick_np_ = p.brick_np;
-   n_left_ = p.n_left;
-   part_line_off_ = p.part_line_off;
-   upload_shared_plan(p.shared, s);
-   breg_.upload(p.breg, s);
-   gmap_line_.upload(p.gmap_line, s);
-   lelem_.upload(p.lelem.empty() ? std::vector<int>{0} : p.lelem, s);
-   belem_.upload(p.belem, s);
-   bmap_.upload(p.bmap, s);
+   const LinePlan p = build_line_plan(ne_, D_, ndofs_, n_owned_, gmap_host_, splits_, bz, plan_options_from_env());
+   line_.upload(p, s);
+   shared_.upload(p.shared, s);
    ECM2_HIP(hipStreamSynchronize(s));  // the uploads read p
-   lelem_off_ = std::move(p.lelem_off);
-   brick_off_ = std::move(p.brick_off);
 }
 
 void PAForm::choose_snapshot(hipStream_t s)
@@ -374,7 +330,7 @@ void PAForm::choose_snapshot(hipStream_t s)
    tsnap_.resize(0);
    // (p >= 3: the same snapshot in the brick kernel was measured and rejected, profiles/r5/ab_c5*.txt)
    const bool ts_tpe = layout_.kind == QLAYOUT_AFFINE && resolved_mode_ == KERNEL_TPE && D_ == 3 && Q_ == 4 &&
-                       (treg_all_ || tlat_all_);
+                       (tpe_.info.treg_all || tpe_.info.tlat_all);
    if (tsnap_pref_ && ts_tpe && have_diff_ && cdiff_.gridfunc() && cdiff_.lvec && !marked_[INTEG_DIFFUSION])
    {
       layout_.tsnap = 1;
@@ -393,7 +349,7 @@ void PAForm::choose_snapshot(hipStream_t s)
          A = cdiff_.scale * (1.0 - cdiff_.slope * cdiff_.t_ref);
          B = cdiff_.scale * cdiff_.slope;
       }
-      if (treg_all_)
+      if (tpe_.info.treg_all)
       {
          tsnap_.resize(std::max(1, ndofs_));
          kern::affine_snapshot(ndofs_, cdiff_.lvec, A, B, tsnap_.data(), s);
@@ -405,7 +361,7 @@ void PAForm::choose_snapshot(hipStream_t s)
          layout_.tsnap = 2;
          const int nlp = tpe_lattice_points(D_);
          tsnap_.resize((size_t)layout_.nblk() * nlp);
-         kern::affine_snapshot_lattice(layout_.nblk(), nlp, lmap_.data(), cdiff_.lvec, A, B, tsnap_.data(), s);
+         kern::affine_snapshot_lattice(layout_.nblk(), nlp, tpe_.lmap.data(), cdiff_.lvec, A, B, tsnap_.data(), s);
       }
    }
 }
@@ -524,10 +480,8 @@ void PAForm::setup_qdata(hipStream_t s)
    }
    else if (layout_.trilinear())
    {
-      QPts qp = {};
-      for (int q = 0; q < Q_ && q < MAX_Q1D; q++) { qp.x[q] = maps_.qpts[q]; }
       kern::setup_trilinear(layout_, Q_, jac_ ? nullptr : enodes_.data(), jac_ ? cfit_.data() : nullptr, W_.data(),
-                            qp, cm, cd, cm_q, cd_q, qd_diff_.data(), qd_mass_.data(), s);
+                            qp_, cm, cd, cm_q, cd_q, qd_diff_.data(), qd_mass_.data(), s);
    }
    else if (jac_)
    {
@@ -636,7 +590,7 @@ void PAForm::mult(const double *x, double *y, hipStream_t s)
       record_start(s);
       kern::restriction_mult((long)ne_ * ND_, ND_, gmap_.data(), x, xe_.data(), s);
       if (ne_) { ECM2_HIP(hipMemsetAsync(ye_.data(), 0, ye_.bytes(), s)); }
-      ApplyArgs a = apply_args(xe_.data(), nullptr, ye_.data(), nullptr, 0, layout_.nblk());
+      ApplyArgs a = apply_args(xe_.data(), nullptr, ye_.data(), nullptr, 0, layout_.nblk(), qdata());
       if (m) { kern::apply_wpe(D_, Q_, true, false, a, true, true, basis_, s); }
       if (d) { kern::apply_wpe(D_, Q_, false, true, a, true, true, basis_, s); }
       kern::restriction_mult_transpose(ndofs_, ND_, csr_off_.data(), csr_idx_.data(), ye_.data(), y, s);
@@ -655,7 +609,7 @@ void PAForm::mult(const double *x, double *y, hipStream_t s)
       record_start(s);
       apply_blocks(x, nullptr, y, nullptr, 0, layout_.nblk(), s);
       record_stop(s);
-      finish_shared(0, n_sh_, y, nullptr, s);
+      finish_shared(0, n_shared(), y, nullptr, s);
       return;
    }
    ECM2_HIP(hipMemsetAsync(y, 0, sizeof(double) * (size_t)ndofs_, s));
@@ -682,7 +636,7 @@ void PAForm::mult_energy(const double *x, double *y, double *en, hipStream_t s)
    record_start(s);
    apply_blocks(x, nullptr, y, nullptr, 0, layout_.nblk(), s, false, en);
    record_stop(s);
-   finish_shared(0, n_sh_, y, nullptr, s);
+   finish_shared(0, n_shared(), y, nullptr, s);
 }
 
 void PAForm::add_mult(const double *x, double *y, double a, hipStream_t s)
@@ -697,23 +651,70 @@ void PAForm::set_scatter(int mode)
 {
    ECM2_VERIFY(mode == SCATTER_PARTIALS || mode == SCATTER_ATOMIC, ERR_ARG, "unknown scatter mode " << mode);
    scatter_ = mode;
-   gmap_line_.resize(0);  // the line kernel's bricks exist only with the partial scatter
+   invalidate_plans(false, true);  // the line kernel's bricks exist only with the partial scatter
    assembled_ = false;
 }
 
-void PAForm::finish_shared(int i0, int i1, double *y, double *yg, hipStream_t s)
+void PAForm::finish_shared(int i0, int i1, double *y, double *yg, hipStream_t s) const
 {
    if (!use_partials()) { return; }
-   // the plan's blocks cover the owned shared dofs [0, n_sh_owned_) then the ghost ones
-   ECM2_VERIFY((i0 == 0 || i0 == n_sh_owned_) && (i1 == n_sh_owned_ || i1 == n_sh_) && i0 <= i1, ERR_INTERNAL,
+   // the plan's blocks cover the owned shared dofs [0, n_sh_owned) then the ghost ones
+   const SharedPlanInfo &P = shared_.info;
+   ECM2_VERIFY((i0 == 0 || i0 == P.n_sh_owned) && (i1 == P.n_sh_owned || i1 == P.n_sh) && i0 <= i1, ERR_INTERNAL,
                "summation range [" << i0 << ", " << i1 << ") is not a plan range");
-   const int b0 = i0 == 0 ? 0 : sh_nblk_owned_, b1 = i1 == n_sh_owned_ ? sh_nblk_owned_ : sh_nblk_;
-   kern::sum_partials(b0, b1, sh_blocks_.data(), sh_runs_.data(), sh_rslots_.data(), sh_pdof_.data(), part_.data(),
-                      n_owned_, y, yg, s);
+   const int b0 = i0 == 0 ? 0 : P.nblk_owned, b1 = i1 == P.n_sh_owned ? P.nblk_owned : P.nblk;
+   kern::sum_partials(b0, b1, shared_.blocks.data(), shared_.runs.data(), shared_.rslots.data(), shared_.pdof.data(),
+                      part_.data(), n_owned_, y, yg, s);
 }
 
-ApplyArgs PAForm::apply_args(const double *x, const double *xg, double *y, double *yg, int b0,
-                             int b1) const
+// What an assembly fixes of a launch: the plan's arrays and flags, the snapshot and its laws.
+void PAForm::build_launch_args()
+{
+   targs_ = TpeArgs{};
+   largs_ = LineArgs{};
+   if (resolved_mode_ == KERNEL_TPE)
+   {
+      TpeArgs &t = targs_;
+      t.lane_flags = tpe_.lane_flags.data();
+      t.treg = tpe_.treg.size() ? tpe_.treg.data() : nullptr;
+      t.treg_all = tpe_.info.treg_all ? 1 : 0;
+      t.tlat_all = tpe_.info.tlat_all ? 1 : 0;
+      t.part_stride = tpe_.info.part_stride;
+      t.lmap = tpe_.lmap.size() ? tpe_.lmap.data() : nullptr;
+      t.xwave = (layout_.kind == QLAYOUT_AFFINE || layout_.kind == QLAYOUT_TRILINEAR) ? 1 : 0;
+      t.tsnap = layout_.tsnap ? tsnap_.data() : nullptr;
+      t.tsnap_kind = layout_.tsnap;
+      t.tmass = layout_.tmass;
+      t.tlaw = layout_.tlaw;
+      if (layout_.tsnap && layout_.tlaw)
+      {
+         t.law_d = point_law_of(cdiff_);
+         if (layout_.tmass == 2 && cmass_.gridfunc()) { t.law_m = point_law_of(cmass_); }
+      }
+      for (int q = 0; q < Q_; q++) { t.qw.x[q] = maps_.qw1[q]; }
+      t.bw = basis_;
+      for (int d = 0; d < MAX_D1D; d++)
+         for (int q = 0; q < MAX_Q1D; q++) { t.bw.B[q + MAX_Q1D * d] = t.qw.x[q] * basis_.B[q + MAX_Q1D * d]; }
+   }
+   else if (resolved_mode_ == KERNEL_LINE)
+   {
+      LineArgs &l = largs_;
+      l.btab = btab();
+      l.lelem = line_.lelem.data();
+      l.lelem_off = line_.lelem_off.empty() ? nullptr : line_.lelem_off.data();
+      if (use_partials()) { l.part_brick = part_.data(); }
+      if (line_.info.brick_bz)
+      {
+         l.brick_bz = line_.info.brick_bz;
+         l.belem = line_.belem.data();
+         l.bmap = line_.bmap.data();
+         l.brick_off = line_.brick_off.data();
+         l.breg = line_.breg.size() ? line_.breg.data() : nullptr;
+      }
+   }
+}
+
+ApplyArgs PAForm::apply_args(const double *x, const double *xg, double *y, double *yg, int b0, int b1, QData q) const
 {
    ApplyArgs a;
    a.kind = layout_.kind;
@@ -723,46 +724,15 @@ ApplyArgs PAForm::apply_args(const double *x, const double *xg, double *y, doubl
    a.blk_end = b1;
    a.n_owned = n_owned_;
    a.pos = layout_.pos;
-   a.lane_flags = lane_flags_.data();
-   a.treg = treg_.size() ? treg_.data() : nullptr;
-   a.treg_all = treg_all_ ? 1 : 0;
-   a.tlat_all = tlat_all_ ? 1 : 0;
-   a.lmap = lmap_.size() ? lmap_.data() : nullptr;
-   for (int q = 0; q < Q_ && q < MAX_Q1D; q++) { a.qp.x[q] = maps_.qpts[q]; a.qw[q] = maps_.qw1[q]; }
-   a.tsnap = layout_.tsnap ? tsnap_.data() : nullptr;
-   a.tsnap_kind = layout_.tsnap;
-   a.tmass = layout_.tmass;
-   a.tlaw = layout_.tlaw;
-   a.cdiag = cdiag_ && (layout_.tsnap || layout_.kind == QLAYOUT_AFFINE_E) ? 1 : 0;
-   if (layout_.tsnap && layout_.tlaw)
-   {
-      a.law_d = point_law_of(cdiff_);
-      if (layout_.tmass == 2 && cmass_.gridfunc()) { a.law_m = point_law_of(cmass_); }
-   }
-   a.xwave = (layout_.kind == QLAYOUT_AFFINE || layout_.kind == QLAYOUT_TRILINEAR) ? 1 : 0;
-   a.part_stride = part_stride_;
-   a.gmap = (resolved_mode_ == KERNEL_TPE) ? gmap_blk_.data()
-            : (resolved_mode_ == KERNEL_LINE) ? gmap_line_.data() : gmap_.data();
-   a.qdd = qd_diff_.data();
-   a.qdm = qd_mass_.data();
+   a.gmap = (resolved_mode_ == KERNEL_TPE) ? tpe_.gmap_blk.data()
+            : (resolved_mode_ == KERNEL_LINE) ? line_.gmap_line.data() : gmap_.data();
+   a.qdd = q.diff;
+   a.qdm = q.mass;
    a.x = x; a.xg = xg; a.y = y; a.yg = yg;
-   a.part = use_partials() ? const_cast<double *>(part_.data()) : nullptr;  // form-owned scratch
-   a.btab = btab();
-   a.lelem = lelem_.data();
-   a.lelem_off = lelem_off_.empty() ? nullptr : lelem_off_.data();
-   if (resolved_mode_ == KERNEL_LINE && use_partials())
-   {
-      a.part_brick = const_cast<double *>(part_.data());
-      a.part = const_cast<double *>(part_.data()) + part_line_off_;  // leftovers: [e][nd] after the bricks
-   }
-   if (resolved_mode_ == KERNEL_LINE && brick_bz_)
-   {
-      a.brick_bz = brick_bz_;
-      a.belem = belem_.data();
-      a.bmap = bmap_.data();
-      a.brick_off = brick_off_.data();
-      a.breg = breg_.size() ? breg_.data() : nullptr;
-   }
+   // LINE: the leftover elements' [e][nd] slots follow the bricks'
+   if (use_partials()) { a.part = part_.data() + (resolved_mode_ == KERNEL_LINE ? line_.info.part_line_off : 0); }
+   a.qp = qp_;
+   a.cdiag = cdiag_ && (layout_.tsnap || layout_.kind == QLAYOUT_AFFINE_E) ? 1 : 0;
    return a;
 }
 
@@ -771,7 +741,7 @@ void PAForm::apply_blocks(const double *x, const double *xg, double *y, double *
 {
    ECM2_VERIFY(assembled_, ERR_STATE, "apply before Assemble");
    ECM2_VERIFY(resolved_mode_ != KERNEL_UNFUSED, ERR_UNSUPPORTED, "block apply needs a fused kernel");
-   if (resolved_mode_ == KERNEL_LINE && brick_bz_)
+   if (resolved_mode_ == KERNEL_LINE && line_.info.brick_bz)
    {
       auto boundary = [&](int b) {
          return b == 0 || b == layout_.nblk() || std::find(splits_.begin(), splits_.end(), b) != splits_.end();
@@ -779,16 +749,16 @@ void PAForm::apply_blocks(const double *x, const double *xg, double *y, double *
       ECM2_VERIFY(boundary(b0) && boundary(b1), ERR_ARG, "apply_blocks [" << b0 << ", " << b1
                                                           << ") cuts a brick: declare the split with set_block_splits");
    }
-   ApplyArgs a = apply_args(x, xg, y, yg, b0, b1);
+   ApplyArgs a = apply_args(x, xg, y, yg, b0, b1, qdata());
    a.latency = latency && layout_.kind == QLAYOUT_AFFINE && have_mass_ && have_diff_ && !layout_.tsnap;
    a.en = en;  // (mult_energy: the snapshot kernel only)
    if (resolved_mode_ == KERNEL_TPE)
    {
-      kern::apply_tpe(D_, Q_, have_mass_, have_diff_, a, basis_, rowtab_.data(), s);
+      kern::apply_tpe(D_, Q_, have_mass_, have_diff_, a, targs_, basis_, rowtab_.data(), s);
    }
    else if (resolved_mode_ == KERNEL_LINE)
    {
-      kern::apply_line(D_, Q_, have_mass_, have_diff_, a, s);
+      kern::apply_line(D_, Q_, have_mass_, have_diff_, a, largs_, s);
    }
    else
    {
@@ -815,7 +785,7 @@ void PAForm::assemble_diagonal(double *diag, hipStream_t s)
    diag_gen_ = gen_;
 }
 
-void PAForm::assemble_diagonal_uncached(double *diag, hipStream_t s)
+void PAForm::assemble_diagonal_uncached(double *diag, hipStream_t s) const
 {
    // The reference's AssembleDiagonal (bilinearform_ext.cpp:370-411) adds every integrator's
    // AssembleDiagonalPA into ONE localY and then zeroes a marked integrator's excluded elements of
@@ -823,66 +793,51 @@ void PAForm::assemble_diagonal_uncached(double *diag, hipStream_t s)
    // too (Mult masks each integrator's output separately, AddMultWithMarkers :753-774).  This
    // library reproduces it: when the second integrator added (S) is marked and excludes elements
    // the first (F) acts on, the diagonal is taken from a copy of the stored (Assemble-time) qdata
-   // with F's entries multiplied by S's element weights (diag_w_, set at Assemble); the Mult's
-   // qdata is swapped back whatever happens.
-   if (diag_integ_ >= 0)
+   // with F's entries multiplied by S's element weights (diag_w_, set at Assemble); the form's own
+   // qdata is only read.
+   if (diag_integ_ < 0)
    {
-      DeviceArray<double> td, tm;
-      td.resize(qd_diff_.size());
-      tm.resize(qd_mass_.size());
-      if (td.size()) { ECM2_HIP(hipMemcpyAsync(td.data(), qd_diff_.data(), td.bytes(), hipMemcpyDeviceToDevice, s)); }
-      if (tm.size()) { ECM2_HIP(hipMemcpyAsync(tm.data(), qd_mass_.data(), tm.bytes(), hipMemcpyDeviceToDevice, s)); }
-      kern::scale_elements(layout_, diag_integ_, diag_w_.data(), td.data(), tm.data(), s);
-      struct Swap
-      {
-         PAForm &f;
-         DeviceArray<double> &d, &m;
-         Swap(PAForm &f_, DeviceArray<double> &d_, DeviceArray<double> &m_) : f(f_), d(d_), m(m_)
-         {
-            std::swap(f.qd_diff_, d);
-            std::swap(f.qd_mass_, m);
-         }
-         ~Swap()
-         {
-            (void)hipDeviceSynchronize();  // the temporaries are freed after this scope
-            std::swap(f.qd_diff_, d);
-            std::swap(f.qd_mass_, m);
-         }
-      } swap(*this, td, tm);
-      diagonal_from_qdata(diag, s);
+      diagonal_from_qdata(diag, qdata(), s);
       return;
    }
-   diagonal_from_qdata(diag, s);
+   DeviceArray<double> td, tm;
+   td.resize(qd_diff_.size());
+   tm.resize(qd_mass_.size());
+   if (td.size()) { ECM2_HIP(hipMemcpyAsync(td.data(), qd_diff_.data(), td.bytes(), hipMemcpyDeviceToDevice, s)); }
+   if (tm.size()) { ECM2_HIP(hipMemcpyAsync(tm.data(), qd_mass_.data(), tm.bytes(), hipMemcpyDeviceToDevice, s)); }
+   kern::scale_elements(layout_, diag_integ_, diag_w_.data(), td.data(), tm.data(), s);
+   diagonal_from_qdata(diag, {td.data(), tm.data()}, s);
+   ECM2_HIP(hipStreamSynchronize(s));  // the temporaries are freed on return
 }
 
-void PAForm::diagonal_from_qdata(double *diag, hipStream_t s)
+void PAForm::diagonal_from_qdata(double *diag, QData q, hipStream_t s) const
 {
    if (resolved_mode_ == KERNEL_TPE && (have_mass_ || have_diff_))
    {
       // thread-per-element diagonal assembled like the Mult (deterministic with partials)
       double *dg = n_owned_ < ndofs_ ? diag + n_owned_ : nullptr;
       if (!use_partials()) { ECM2_HIP(hipMemsetAsync(diag, 0, sizeof(double) * (size_t)ndofs_, s)); }
-      ApplyArgs a = apply_args(nullptr, nullptr, diag, dg, 0, layout_.nblk());
+      ApplyArgs a = apply_args(nullptr, nullptr, diag, dg, 0, layout_.nblk(), q);
       DeviceArray<double> fd, fm;
       if (expand_needed())
       {
-         expand_compressed(fd, fm, s);  // per-point qdata for the diagonal's tables
+         expand_compressed(q, fd, fm, s);  // per-point qdata for the diagonal's tables
          a.kind = expand_kind();
          a.qdd = fd.data();
          a.qdm = fm.data();
       }
-      kern::diagonal_tpe(D_, Q_, have_mass_, have_diff_, a, basis_, drowtab_.data(), s);
-      finish_shared(0, n_sh_, diag, dg, s);
+      kern::diagonal_tpe(D_, Q_, have_mass_, have_diff_, a, targs_, basis_, drowtab_.data(), s);
+      finish_shared(0, n_shared(), diag, dg, s);
       if (fd.size()) { ECM2_HIP(hipStreamSynchronize(s)); }  // the temporaries are freed on return
       return;
    }
    ECM2_HIP(hipMemsetAsync(diag, 0, sizeof(double) * (size_t)ndofs_, s));
    DeviceArray<double> fd, fm;
    int kind = layout_.kind;
-   const double *qdd = qd_diff_.data(), *qdm = qd_mass_.data();
+   const double *qdd = q.diff, *qdm = q.mass;
    if (expand_needed())
    {
-      expand_compressed(fd, fm, s);
+      expand_compressed(q, fd, fm, s);
       kind = expand_kind();
       qdd = fd.data();
       qdm = fm.data();
@@ -892,7 +847,7 @@ void PAForm::diagonal_from_qdata(double *diag, hipStream_t s)
    if (fd.size()) { ECM2_HIP(hipStreamSynchronize(s)); }  // the temporaries are freed on return
 }
 
-void PAForm::expand_compressed(DeviceArray<double> &fd, DeviceArray<double> &fm, hipStream_t s) const
+void PAForm::expand_compressed(QData q, DeviceArray<double> &fd, DeviceArray<double> &fm, hipStream_t s) const
 {
    QLayout L = layout_;
    L.kind = expand_kind();
@@ -903,8 +858,6 @@ void PAForm::expand_compressed(DeviceArray<double> &fd, DeviceArray<double> &fm,
       ECM2_HIP(hipMemsetAsync(fd.data(), 0, fd.bytes(), s));
       ECM2_HIP(hipMemsetAsync(fm.data(), 0, fm.bytes(), s));
    }
-   QPts qp = {};
-   for (int q = 0; q < Q_ && q < MAX_Q1D; q++) { qp.x[q] = maps_.qpts[q]; }
    if (layout_.tsnap)
    {
       // beta (and a mass law of the same field) at the points from the snapshot -- the field as
@@ -916,7 +869,7 @@ void PAForm::expand_compressed(DeviceArray<double> &fd, DeviceArray<double> &fm,
       if (layout_.tsnap == 2)
       {
          tdof.resize(std::max(1, ndofs_));
-         kern::lattice_to_dofs(layout_.nblk(), tpe_lattice_points(D_), lmap_.data(), tsnap_.data(), tdof.data(), s);
+         kern::lattice_to_dofs(layout_.nblk(), tpe_lattice_points(D_), tpe_.lmap.data(), tsnap_.data(), tdof.data(), s);
          tv = tdof.data();
       }
       CoeffDesc cs = cdiff_;
@@ -932,16 +885,16 @@ void PAForm::expand_compressed(DeviceArray<double> &fd, DeviceArray<double> &fm,
          cm.emask = nullptr;
          cm_q = coeff_points(cm, ctm, s);
       }
-      kern::tsnap_expand(layout_, Q_, W_.data(), qd_diff_.data(), qd_mass_.data(), cd_q, cm_q, fd.data(),
+      kern::tsnap_expand(layout_, Q_, W_.data(), q.diff, q.mass, cd_q, cm_q, fd.data(),
                          fm.data(), s);
       ECM2_HIP(hipStreamSynchronize(s));  // the temporaries are freed on return
       return;
    }
    if (layout_.trilinear())
    {
-      kern::trilinear_expand(layout_, Q_, qd_diff_.data(), qd_mass_.data(), qp, fd.data(), fm.data(), s);
+      kern::trilinear_expand(layout_, Q_, q.diff, q.mass, qp_, fd.data(), fm.data(), s);
    }
-   else { kern::affine_expand(layout_, Q_, qd_diff_.data(), qd_mass_.data(), fd.data(), fm.data(), s); }
+   else { kern::affine_expand(layout_, Q_, q.diff, q.mass, fd.data(), fm.data(), s); }
 }
 
 void PAForm::restriction_mult(const double *x, double *xe, hipStream_t s)
@@ -960,12 +913,12 @@ void PAForm::integrator_add_mult(int kind, const double *xe, double *ye, hipStre
    ECM2_VERIFY(assembled_, ERR_STATE, "AddMultPA before Assemble");
    ECM2_VERIFY((kind == INTEG_MASS && have_mass_) || (kind == INTEG_DIFFUSION && have_diff_),
                ERR_ARG, "integrator " << kind << " not present");
-   ApplyArgs a = apply_args(xe, nullptr, ye, nullptr, 0, layout_.nblk());
+   ApplyArgs a = apply_args(xe, nullptr, ye, nullptr, 0, layout_.nblk(), qdata());
    a.gmap = gmap_.data();
    DeviceArray<double> fd, fm;
    if (expand_needed())
    {
-      expand_compressed(fd, fm, s);
+      expand_compressed(qdata(), fd, fm, s);
       a.kind = expand_kind();
       a.qdd = fd.data();
       a.qdm = fm.data();
@@ -982,7 +935,7 @@ void PAForm::get_qdata(int kind, double *out, hipStream_t s)
    DeviceArray<double> fd, fm;
    const bool tl = expand_needed();  // TRILINEAR(_E), or a diffusion-only AFFINE(_E) form
    const bool aff = layout_.affine() && !tl;
-   if (tl) { expand_compressed(fd, fm, s); }  // decoded as expand_kind() below
+   if (tl) { expand_compressed(qdata(), fd, fm, s); }  // decoded as expand_kind() below
    const int kind_h = tl ? expand_kind() : layout_.kind;
    DeviceArray<double> &src = tl ? (diff ? fd : fm) : ((diff && !aff) ? qd_diff_ : qd_mass_);
    std::vector<double> h(src.size()), hc(aff ? qd_diff_.size() : 0);
@@ -996,13 +949,9 @@ void PAForm::get_qdata(int kind, double *out, hipStream_t s)
    }
    ECM2_HIP(hipStreamSynchronize(s));
    const int nc = diff ? (layout_.kind == QLAYOUT_NATIVE9 ? 9 : 6) : 1;
-   std::vector<int> invp;
-   if (!perm_host_.empty())
-   {
-      invp.resize(ne_);
-      for (int i = 0; i < ne_; i++) { invp[perm_host_[i]] = i; }
-   }
-   auto inv_perm = [&](int e) { return invp[e]; };
+   // (blocked layouts: the TPE plan's element order)
+   std::vector<int> invp(layout_.blocked() ? ne_ : 0);
+   for (size_t i = 0; i < invp.size(); i++) { invp[tpe_.perm[i]] = (int)i; }
    for (int e = 0; e < ne_; e++)
       for (int c = 0; c < nc; c++)
          for (int q = 0; q < NQ_; q++)
@@ -1017,7 +966,7 @@ void PAForm::get_qdata(int kind, double *out, hipStream_t s)
             }
             else
             {
-               const int ip = perm_host_.empty() ? e : inv_perm(e);
+               const int ip = invp[e];
                const int blk = ip / 64, lane = ip % 64;
                if (aff)
                {

@@ -13,13 +13,18 @@
 // stream (the reference uses the null stream, forall.hpp:782).
 //
 // The fused kernels' scatter planning (element order, merge flags, dof maps, lattice blocks and
-// bricks, partial slots, the summation plan) is host-only code in scatter_plan.hpp; this class
-// uploads what those functions return and keeps the scalars the launches need.
+// bricks, partial slots, the summation plan) is host-only code in scatter_plan.hpp.  The form owns
+// what those functions return as three plan objects (plan_dev.hpp): tpe_ (p <= 2), line_ (p >= 3)
+// and shared_ (the summation pass of whichever is in use); a setter that feeds a plan's builder
+// invalidates it (invalidate_plans), Assemble rebuilds what is not valid.  A launch takes two kinds
+// of arguments (kernels.hpp): TpeArgs / LineArgs, built once at the end of Assemble from the plan
+// and the snapshot, and ApplyArgs, filled per call (vectors, block range, the qdata to read).
 #pragma once
 
 #include "common.hpp"
 #include "fe.hpp"
 #include "kernels.hpp"
+#include "plan_dev.hpp"
 
 #include <memory>
 #include <utility>
@@ -27,8 +32,6 @@
 
 namespace ecm2
 {
-
-struct SharedPlan;  // scatter_plan.hpp
 
 enum KernelMode : int
 {
@@ -108,21 +111,21 @@ public:
    // Blocks >= b are applied with the one-block-per-workgroup latency kernel (apply_blocks
    // latency = true): no cross-wave face assembly there.  -1: none.
    void set_latency_from(int b);
-   int n_bricks() const { return n_bricks_; }
+   int n_bricks() const { return line_.info.n_bricks; }
    // units (p <= 2 blocks, p >= 3 bricks) whose dofs the fused kernel computes from 5 ints
    // instead of reading the map
    int lattice_units() const
    {
       if (resolved_mode_ == KERNEL_TPE)
       {
-         return (layout_.kind == QLAYOUT_AFFINE || layout_.kind == QLAYOUT_TRILINEAR) ? n_treg_ : 0;
+         return (layout_.kind == QLAYOUT_AFFINE || layout_.kind == QLAYOUT_TRILINEAR) ? tpe_.info.n_treg : 0;
       }
-      return (resolved_mode_ == KERNEL_LINE && breg_.size()) ? n_bricks_ : 0;
+      return (resolved_mode_ == KERNEL_LINE && line_.breg.size()) ? n_bricks() : 0;
    }
-   int n_units() const { return resolved_mode_ == KERNEL_TPE ? layout_.nblk() : n_bricks_; }
+   int n_units() const { return resolved_mode_ == KERNEL_TPE ? layout_.nblk() : n_bricks(); }
    // p <= 2 blocks with face-grouped partial slots but map-addressed dofs (a numbering that is not a lattice)
-   int lattice_slot_units() const { return resolved_mode_ == KERNEL_TPE ? n_tlat_ : 0; }
-   int brick_bz() const { return brick_bz_; }
+   int lattice_slot_units() const { return resolved_mode_ == KERNEL_TPE ? tpe_.info.n_tlat : 0; }
+   int brick_bz() const { return line_.info.brick_bz; }
    // BilinearForm::AddDomainIntegrator(integ[, elem_marker]) (bilinearform.cpp:231-242): with a
    // marker (host marker[n_marker], 0 / 1 per attribute), the integrator acts on the elements
    // whose attribute a has a > 0 and marker[a - 1] != 0 only (AddMultWithMarkers,
@@ -165,12 +168,12 @@ public:
    // block a workgroup with one quadrature plane per wave).
    void apply_blocks(const double *x, const double *xg, double *y, double *yg, int b0, int b1,
                      hipStream_t s, bool latency = false, double *en = nullptr);
-   void finish_shared(int i0, int i1, double *y, double *yg, hipStream_t s);
-   int n_shared() const { return n_sh_; }
-   int n_shared_owned() const { return n_sh_owned_; }
-   long n_partial_slots() const { return n_slots_; }
-   long n_summation_runs() const { return n_runs_; }
-   long n_explicit_runs() const { return n_explicit_runs_; }
+   void finish_shared(int i0, int i1, double *y, double *yg, hipStream_t s) const;
+   int n_shared() const { return shared_.info.n_sh; }
+   int n_shared_owned() const { return shared_.info.n_sh_owned; }
+   long n_partial_slots() const { return shared_.info.n_slots; }
+   long n_summation_runs() const { return shared_.info.n_runs; }
+   long n_explicit_runs() const { return shared_.info.n_explicit_runs; }
    int nblocks() const { return layout_.nblk(); }
    bool has_mass() const { return have_mass_; }
    bool has_diffusion() const { return have_diff_; }
@@ -183,35 +186,44 @@ public:
    // qdata in the reference's native layout, copied to the host.
    void get_qdata(int kind, double *out_host, hipStream_t s);
 
-   // HIP-event timing of the dominant (apply) kernel.
+   // HIP-event timing of the dominant (apply) kernel; record_start / record_stop bracket one
+   // (the distributed form brackets its own apply_blocks calls).
    void timing_enable(bool on);
    bool timing_on() const { return timing_; }
    void timing_get(double *total_ms, long *launches);
+   void record_start(hipStream_t s);
+   void record_stop(hipStream_t s);
    size_t algorithmic_bytes() const;
 
 private:
+   // stored qdata to read: the form's own, or a caller's scaled copy (the marker diagonal)
+   struct QData
+   {
+      const double *diff, *mass;
+   };
+   QData qdata() const { return {qd_diff_.data(), qd_mass_.data()}; }
    void ensure_csr();
    void ensure_work(hipStream_t s);
-   void record_start(hipStream_t s);
-   void record_stop(hipStream_t s);
+   // a setter that feeds build_tpe_plan / build_line_plan drops that plan: Assemble rebuilds it
+   void invalidate_plans(bool tpe, bool line);
    // assemble()'s steps, in order: kernel mode and qdata layout; the fused kernel's scatter plan
    // (built by scatter_plan.hpp's host functions unless the cached one still holds, then uploaded);
    // the coefficient snapshot; setup_qdata; the marker diagonal's weights
    void resolve_layout(hipStream_t s);
    void plan_tpe(hipStream_t s);
    void plan_line(hipStream_t s);
-   void upload_shared_plan(const SharedPlan &p, hipStream_t s);
    void choose_snapshot(hipStream_t s);
    void setup_marker_diagonal(hipStream_t s);
-   ApplyArgs apply_args(const double *x, const double *xg, double *y, double *yg, int b0,
-                        int b1) const;
+   // the launch arguments fixed by an assembly (targs_ / largs_), and one call's
+   void build_launch_args();
+   ApplyArgs apply_args(const double *x, const double *xg, double *y, double *yg, int b0, int b1, QData q) const;
    // qdata of the integrators present (resized, padding cleared, coefficients projected, setup
    // kernel)
    void setup_qdata(hipStream_t s);
    // element weights [ne] of integrator kind k: 1 / 0 per its attribute marker, all 1 unmarked
    std::vector<double> marker_weights(int k) const;
-   void diagonal_from_qdata(double *diag, hipStream_t s);
-   void assemble_diagonal_uncached(double *diag, hipStream_t s);
+   void diagonal_from_qdata(double *diag, QData q, hipStream_t s) const;
+   void assemble_diagonal_uncached(double *diag, hipStream_t s) const;
    // TRILINEAR(_E) forms and diffusion-only AFFINE(_E) forms: their per-point qdata in the BLOCKED
    // (p <= 2) or NATIVE (p >= 3) layout, expand_kind() (temporaries of the caller) for the
    // diagonal, the E-vector apply and the qdata export
@@ -222,28 +234,24 @@ private:
    // coefficient values at the quadrature points ([e][q], tmp holds computed ones)
    const double *coeff_points(const CoeffDesc &c, DeviceArray<double> &tmp, hipStream_t s) const;
    int expand_kind() const { return layout_.blocked() ? QLAYOUT_BLOCKED : QLAYOUT_NATIVE; }
-   void expand_compressed(DeviceArray<double> &fd, DeviceArray<double> &fm, hipStream_t s) const;
+   // (q: the stored compressed qdata to expand)
+   void expand_compressed(QData q, DeviceArray<double> &fd, DeviceArray<double> &fm, hipStream_t s) const;
 
- public:
-   void record_start_public(hipStream_t s) { record_start(s); }
-   void record_stop_public(hipStream_t s) { record_stop(s); }
-
- private:
    int ne_, order_, ndofs_, n_owned_, D_, Q_, ND_, NQ_;
    DofToQuad maps_;
+   QPts qp_ = {};                   // maps_.qpts as a kernel argument
    Basis1D basis_, basis1_;
    QLayout layout_;
    int mode_ = KERNEL_AUTO, resolved_mode_ = KERNEL_AUTO;
    int scatter_ = SCATTER_PARTIALS;
-   int n_sh_ = 0, n_sh_owned_ = 0;
-   long n_slots_ = 0;
-   // second-pass plan (see finish_shared, kern::sum_partials): runs [nrun + 1][12], the
-   // first slots of holders beyond the fourth, blocks [nblk][2] (owned runs' blocks first)
-   DeviceArray<int> sh_runs_, sh_rslots_, sh_blocks_;
-   DeviceArray<int> sh_pdof_;       // plan entry -> dof (runs whose dofs are not affine read it)
-   long n_runs_ = 0, n_explicit_runs_ = 0;
-   int sh_nblk_owned_ = 0, sh_nblk_ = 0;
-   DeviceArray<double> part_;                       // partial slots: TPE [blk][nd][64]; LINE [bricks | [e][nd]]
+   // the fused kernels' scatter plans (plan_dev.hpp) and the launch arguments of the last Assemble
+   TpePlanDev tpe_;
+   LinePlanDev line_;
+   SharedPlanDev shared_;
+   TpeArgs targs_;
+   LineArgs largs_;
+   // partial slots: TPE [blk][part_stride]; LINE [bricks | [e][nd]] (scratch every apply and diagonal writes)
+   mutable DeviceArray<double> part_;
    bool assembled_ = false;
    DeviceArray<double> diag_cache_;  // the diagonal of assembly diag_gen_ (assemble_diagonal)
    long diag_gen_ = -1;
@@ -261,38 +269,16 @@ private:
 
    std::vector<int> gmap_host_;
    DeviceArray<int> gmap_;          // native [e][nd]
-   DeviceArray<int> gmap_blk_;      // blocked [blk][nd][64] (internal element order)
-   DeviceArray<int> gmap_line_;     // LINE: [e][nd] dof | shared << 30 | sign << 31
-   DeviceArray<int> lelem_;         // LINE: elements outside bricks
-   std::vector<int> lelem_off_;     // LINE: listed elements of block b = [lelem_off_[b], lelem_off_[b+1])
    std::vector<int> splits_;        // apply_blocks range boundaries besides 0 / nblk
-   int n_bricks_ = 0, brick_bz_ = 0, brick_np_ = 0;  // LINE bricks: count, 2 x 2 x bz, lattice points
-   DeviceArray<int> belem_, bmap_;  // LINE bricks: [nbrick][4 bz] elements, [nbrick][np] lattice map
-   DeviceArray<int> breg_;          // LINE bricks, lattice-numbered: [nbrick][8] (base, sx, sy, sz, face mask)
-   DeviceArray<int> treg_;          // TPE blocks: [nblk][8] (base, sx, sy, sz, face mask, -, -, flag 1 regular / 2 lattice slots)
-   bool treg_all_ = false;          // every TPE block regular: face-grouped slots only
+   std::vector<int> user_perm_;     // set_element_order's (empty: none, the TPE plan derives one)
    bool cdiag_ = false;             // snapshot forms: every element's C diagonal (axis-aligned: the diagonal flux)
    DeviceArray<int> cdflag_;        // its test's device scratch
-   bool tlat_all_ = false;          // every TPE block a lattice-map block (treg flag 2)
-   int n_treg_ = 0;                 // regular TPE blocks
-   int n_tlat_ = 0;                 // TPE blocks with face-grouped slots but map-addressed dofs (treg flag 2)
-   DeviceArray<int> lmap_;          // their block lattice maps [nblk][tpe_lattice_points] (tpe_lattice_slot order)
-   int part_stride_ = 0;            // TPE partial slots per block
-   int plan_kind_ = -1;             // qdata layout the TPE plan (merges, regular blocks, slots) was built for
-   std::vector<int> brick_off_;     // LINE bricks of block b = [brick_off_[b], brick_off_[b+1])
-   long part_line_off_ = 0;         // LINE: leftover elements' partial slots start here
-   int n_left_ = 0;                 // LINE: elements outside bricks
    int line_bricks_ = -1;           // requested brick mode (set_line_bricks)
    bool affine_ = false;            // every element a parallelepiped (set_element_nodes)
    bool compress_ = true;           // set_geometry_compression
    bool tsnap_pref_ = true;         // set_coefficient_snapshot
    DeviceArray<double> tsnap_;      // coefficient snapshot T' = A + B T (local L-vector)
    int latency_from_ = -1;          // set_latency_from
-   bool perm_auto_ = false;         // perm_host_ was derived (not the caller's)
-   DeviceArray<int> lane_flags_;    // [blk][64] in-wave merge flags
-   std::vector<int> perm_host_;     // internal position -> caller element (empty: identity)
-   DeviceArray<int> pos_;           // caller element -> internal position
-   DeviceArray<int> perm_dev_;      // internal position -> caller element
    DeviceArray<int> csr_off_, csr_idx_;
    DeviceArray<double> enodes_;     // [e][3][8]
    DeviceArray<double> cfit_;       // TRILINEAR from Jacobians: fitted map coefficients [e][21]

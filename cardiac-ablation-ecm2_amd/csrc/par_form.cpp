@@ -244,9 +244,9 @@ void ParPAForm::stage_pack(const double *x_true, double *y_true, hipStream_t s)
 
 void ParPAForm::stage_boundary(const double *x_true, double *y_true)
 {
-   local_->record_start_public(cs_);
+   local_->record_start(cs_);
    local_->apply_blocks(x_true, xg_.data(), y_true, yg_.data(), b_int(), local_->nblocks(), cs_, true);
-   local_->record_stop_public(cs_);
+   local_->record_stop(cs_);
    // ghost dofs are touched only by boundary elements: their sums are complete here (OVERLAP:
    // the ghost outputs are discarded, nothing to sum)
    if (!part_.overlap) { local_->finish_shared(local_->n_shared_owned(), local_->n_shared(), y_true, yg_.data(), cs_); }
@@ -255,9 +255,9 @@ void ParPAForm::stage_boundary(const double *x_true, double *y_true)
 
 void ParPAForm::stage_interior(const double *x_true, double *y_true, hipStream_t s)
 {
-   local_->record_start_public(s);
+   local_->record_start(s);
    local_->apply_blocks(x_true, xg_.data(), y_true, yg_.data(), 0, b_int(), s);
-   local_->record_stop_public(s);
+   local_->record_stop(s);
 }
 
 void ParPAForm::stage_finish(double *y_true, hipStream_t s)
@@ -296,9 +296,9 @@ void ParPAForm::stage_serial_apply(const double *x_true, double *y_true, hipStre
       if (part_.n_owned) { ECM2_HIP(hipMemsetAsync(y_true, 0, sizeof(double) * part_.n_owned, s)); }
       if (part_.n_ghost) { ECM2_HIP(hipMemsetAsync(yg_.data(), 0, sizeof(double) * part_.n_ghost, s)); }
    }
-   local_->record_start_public(s);
+   local_->record_start(s);
    local_->apply_blocks(x_true, xg_.data(), y_true, yg_.data(), 0, local_->nblocks(), s);
-   local_->record_stop_public(s);
+   local_->record_stop(s);
    if (!part_.overlap) { local_->finish_shared(local_->n_shared_owned(), local_->n_shared(), y_true, yg_.data(), s); }
 }
 

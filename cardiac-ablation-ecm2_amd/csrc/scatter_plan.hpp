@@ -4,7 +4,8 @@
 // element order, the in-wave / cross-wave merge flags, the blocked and encoded dof maps, which
 // 4 x 4 x 4 blocks and 2 x 2 x bz bricks are lattice units, the partial-slot numbering and the
 // run-compressed summation plan kern::sum_partials executes.  Free functions over plain vectors
-// (like bricks.hpp, partition.hpp): no device, no stream, no PAForm.  PAForm::assemble calls the
+// (like bricks.hpp, partition.hpp): no device, no stream, no PAForm.  Each plan's scalars are a small
+// ...Info base that its device-side owner (plan_dev.hpp) copies whole.  PAForm::assemble calls the
 // builders and uploads what they return; tests/cpp/plan_check.cpp replays them on the host.
 #pragma once
 
@@ -23,14 +24,17 @@ PlanOptions plan_options_from_env();
 
 // Second-pass plan of the deterministic scatter (kern::sum_partials): every dof not held exactly
 // once, the owned ones first, then the ghosts.
-struct SharedPlan
+struct SharedPlanInfo
+{
+   int n_sh = 0, n_sh_owned = 0, nblk_owned = 0, nblk = 0;
+   long n_slots = 0, n_runs = 0, n_explicit_runs = 0;
+};
+struct SharedPlan : SharedPlanInfo
 {
    std::vector<int> runs;    // [n_runs + 1][12] run descriptors, sentinel row last
    std::vector<int> rslots;  // first slots of every run's holders (read for holders past the fourth)
    std::vector<int> blocks;  // [nblk][4]: first run, end run, first entry, entries | explicit << 30
    std::vector<int> pdof;    // plan entry -> dof
-   int n_sh = 0, n_sh_owned = 0, nblk_owned = 0, nblk = 0;
-   long n_slots = 0, n_runs = 0, n_explicit_runs = 0;
 };
 // hcount[d]: holders of dof d; (hdof[i], hslot[i]): the holders of the dofs held more than once
 SharedPlan build_shared_plan(int ndofs, int n_owned, const std::vector<int> &hcount, const std::vector<int> &hdof,
@@ -44,7 +48,12 @@ inline LatticeXYZ block_lattice_xyz(int D, int lane, int a)
 }
 
 // Thread-per-element kernel (p <= 2): 64 elements per block, one per lane.
-struct TpePlan
+struct TpePlanInfo
+{
+   int n_treg = 0, n_tlat = 0, part_stride = 0;  // regular blocks, lattice-slot blocks, partial slots per block
+   bool treg_all = false, tlat_all = false;      // every block regular / a lattice-slot block
+};
+struct TpePlan : TpePlanInfo
 {
    std::vector<int> perm;       // internal position -> caller element (the order used)
    bool perm_derived = false;   // derived here (face_brick_order per apply segment), not the caller's
@@ -53,8 +62,6 @@ struct TpePlan
    std::vector<int> lane_flags; // [blk][64] merge flags (build_merge_plan)
    std::vector<int> treg;       // [blk][8]: base, sx, sy, sz, face mask, -, -, 1 regular / 2 lattice slots; empty: none
    std::vector<int> lmap;       // [blk][tpe_lattice_points] lattice maps; empty: no lattice-slot block
-   int n_treg = 0, n_tlat = 0, part_stride = 0;
-   bool treg_all = false, tlat_all = false;
    SharedPlan shared;
 };
 // perm_host empty: derive the order.  lattice_layout: the AFFINE / TRILINEAR qdata layouts (cross-wave
@@ -64,7 +71,12 @@ TpePlan build_tpe_plan(int ne, int D, int ndofs, int n_owned, const std::vector<
                        bool lattice_layout, const PlanOptions &opt);
 
 // Line kernel family (p >= 3): bricks of 2 x 2 x bz elements, the other elements one by one.
-struct LinePlan
+struct LinePlanInfo
+{
+   int n_bricks = 0, brick_bz = 0, brick_np = 0, n_left = 0;  // bricks, 2 x 2 x bz, lattice points, elements outside bricks
+   long part_line_off = 0;  // the leftover elements' [e][nd] partial slots start here
+};
+struct LinePlan : LinePlanInfo
 {
    std::vector<int> gmap_line;  // [e][nd]: dof | shared << 30 | sign << 31
    std::vector<int> lelem;      // elements outside bricks
@@ -73,8 +85,6 @@ struct LinePlan
    std::vector<int> bmap;       // [nbrick][np] encoded lattice maps
    std::vector<int> brick_off;  // bricks of block b: [brick_off[b], brick_off[b + 1])
    std::vector<int> breg;       // [nbrick][8]: base, sx, sy, sz, face mask; empty unless every brick is regular
-   int n_bricks = 0, brick_bz = 0, brick_np = 0, n_left = 0;
-   long part_line_off = 0;      // the leftover elements' [e][nd] partial slots start here
    SharedPlan shared;
 };
 LinePlan build_line_plan(int ne, int D, int ndofs, int n_owned, const std::vector<int> &gmap_host,
