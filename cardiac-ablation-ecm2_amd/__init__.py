@@ -85,6 +85,16 @@ def load_library(path: str = LIB_PATH):
         "ecm2_pa_form_add_integrator_marked": (i32, [vp, i32, i32, vp, vp, vp, i32]),
         "ecm2_pa_form_set_attributes": (i32, [vp, vp]),
         "ecm2_mesh_quadrature_points": (i32, [vp, i32, vp]),
+        "ecm2_mesh_boundary_info": (i32, [vp, ip]),
+        "ecm2_mesh_get_boundary": (i32, [vp, vp, vp]),
+        "ecm2_mesh_set_boundary_attributes": (i32, [vp, vp]),
+        "ecm2_mesh_get_boundary_nodes": (i32, [vp, vp]),
+        "ecm2_h1space_get_boundary_map": (i32, [vp, vp]),
+        "ecm2_pa_form_set_boundary": (i32, [vp, i32, vp, vp, vp, i32]),
+        "ecm2_pa_form_set_boundary_detj": (i32, [vp, vp]),
+        "ecm2_pa_form_add_boundary_integrator": (i32, [vp, i32, i32, vp, vp, i32]),
+        "ecm2_pa_form_get_boundary_qdata": (i32, [vp, i32, vp, vp]),
+        "ecm2_pa_form_boundary_info": (i32, [vp, ip, ip, ip, ip]),
         "ecm2_mesh_destroy": (None, [vp]),
         "ecm2_h1space_create": (i32, [vp, i32, i32, pp]),
         "ecm2_h1space_info": (i32, [vp, ip, ip, ip]),
@@ -141,12 +151,21 @@ def load_library(path: str = LIB_PATH):
     return lib
 
 
+def _error(rc: int) -> ECM2Error:
+    msg = _lib.ecm2_last_error().decode(errors="replace")
+    err = ECM2Error(f"ecm2 error {rc}: {msg}")
+    err.code = rc
+    return err
+
+
 def _check(rc: int):
+    # The exception is built in _error and raised from an expression: no frame of the traceback holds
+    # it in a local.  (A local `err` here made a cycle err -> traceback -> this frame -> err that kept
+    # every frame of the traceback -- the caller's forms, tensors, captured graphs -- alive until some
+    # later cyclic collection, which can fall inside a stream capture, where their finalizers'
+    # synchronising calls are illegal.)
     if rc != 0:
-        msg = _lib.ecm2_last_error().decode(errors="replace")
-        err = ECM2Error(f"ecm2 error {rc}: {msg}")
-        err.code = rc
-        raise err
+        raise _error(rc)
 
 
 def pcg_last_converged() -> bool:
@@ -263,6 +282,36 @@ class Mesh:
         assert a.shape == (self.GetNE(),)
         _check(_lib.ecm2_mesh_set_attributes(self._h, _np_ptr(a)))
 
+    def GetNBE(self) -> int:
+        """Mesh::GetNBE: boundary elements (quadrilaterals)."""
+        n = ctypes.c_int()
+        _check(_lib.ecm2_mesh_boundary_info(self._h, ctypes.byref(n)))
+        return n.value
+
+    def boundary(self) -> np.ndarray:
+        """Vertices of the boundary quads [nbe][4], in each quad's own order."""
+        out = np.empty((self.GetNBE(), 4), np.int32)
+        _check(_lib.ecm2_mesh_get_boundary(self._h, _np_ptr(out), None))
+        return out
+
+    def GetBdrAttributes(self) -> np.ndarray:
+        """Boundary attributes [nbe] (Mesh::GetBdrAttribute)."""
+        out = np.empty(self.GetNBE(), np.int32)
+        _check(_lib.ecm2_mesh_get_boundary(self._h, None, _np_ptr(out)))
+        return out
+
+    def SetBdrAttributes(self, attr):
+        """Mesh::SetBdrAttribute for every boundary element."""
+        a = np.ascontiguousarray(attr, np.int32)
+        assert a.shape == (self.GetNBE(),)
+        _check(_lib.ecm2_mesh_set_boundary_attributes(self._h, _np_ptr(a)))
+
+    def boundary_nodes(self) -> np.ndarray:
+        """Corners of the boundary quads [nbe][3][4], lexicographic in the quad's frame (v0, v1, v3, v2)."""
+        out = np.empty((self.GetNBE(), 3, 4), np.float64)
+        _check(_lib.ecm2_mesh_get_boundary_nodes(self._h, _np_ptr(out)))
+        return out
+
     def element_order(self, kind: int) -> np.ndarray:
         """0 native, 1 brick (Cartesian only), 2 Morton order of centroids."""
         out = np.empty(self.GetNE(), np.int32)
@@ -349,6 +398,13 @@ class H1Space:
         return out
 
     GetEssentialTrueDofs = boundary_dofs
+
+    def boundary_map(self) -> np.ndarray:
+        """Dofs of every boundary element [nbe][(p+1)^2], lexicographic in the quad's frame (xi along
+        v0 -> v1, eta along v0 -> v3): the frame of Mesh.boundary_nodes()."""
+        out = np.empty((self.mesh.GetNBE(), (self.order + 1) ** 2), np.int32)
+        _check(_lib.ecm2_h1space_get_boundary_map(self._h, _np_ptr(out)))
+        return out
 
     def dof_coords(self) -> np.ndarray:
         out = np.empty((self.ndofs, 3), np.float64)
@@ -597,6 +653,57 @@ class BilinearForm:
             self._marked = True
         self._integs.append(integ)
 
+    def SetBoundary(self, q1d: int = 0):
+        """Hand the form the space's boundary elements (dof map, attributes, corners).  q1d = 0:
+        MassIntegrator's rule on the boundary quad, p + 1 points; p + 2 is supported too.
+        AddBoundaryIntegrator calls it on its own."""
+        bm, at, bn = self.fes.boundary_map(), self.fes.mesh.GetBdrAttributes(), self.fes.mesh.boundary_nodes()
+        _check(_lib.ecm2_pa_form_set_boundary(self._h, bm.shape[0], _np_ptr(bm), _np_ptr(at), _np_ptr(bn), q1d))
+        self._bdr_set = True
+
+    def SetBoundaryDetJ(self, detj):
+        """FaceGeometricFactors::detJ at the face rule, torch CUDA float64 [nbe][q1d^2], instead of
+        the corners."""
+        if not getattr(self, "_bdr_set", False):
+            self.SetBoundary()
+        nbe, _, _, q = self.BoundaryInfo()
+        _check_points(self, detj, ((),), nbe, q * q, flat_ok=True)
+        self._keep.append(detj)
+        _check(_lib.ecm2_pa_form_set_boundary_detj(self._h, _dev_ptr(detj)))
+
+    def AddBoundaryIntegrator(self, integ, bdr_marker=None):
+        """BilinearForm::AddBoundaryIntegrator(new MassIntegrator(h)[, bdr_marker]) -- the Robin term.
+        h: ConstantCoefficient or QuadratureCoefficient (CUDA float64 [nbe][q1d^2], boundary element
+        order); bdr_marker: 0 / 1 per boundary attribute."""
+        if not getattr(self, "_bdr_set", False):
+            self.SetBoundary()
+        nbe, _, _, q = self.BoundaryInfo()
+        c = integ.coeff
+        if isinstance(c, (ConstantCoefficient, QuadratureCoefficient)):
+            kind, data, _ = _integrator_args(c, self._keep, nbe, q * q, None)
+        else:  # the library refuses the kind (ECM2_ERR_ARG)
+            kind, data, _ = _integrator_args(c, self._keep, None, None, self.fes.ndofs)
+        mk, n = None, 0
+        if bdr_marker is not None:
+            mk = np.ascontiguousarray(bdr_marker, np.int32)
+            n = mk.size
+        _check(_lib.ecm2_pa_form_add_boundary_integrator(self._h, integ.kind, kind, data,
+                                                         _np_ptr(mk) if mk is not None else None, n))
+
+    def BoundaryInfo(self):
+        """(boundary elements, boundary integrators, faces kept by the last Assemble, face rule q1d)."""
+        v = [ctypes.c_int() for _ in range(4)]
+        _check(_lib.ecm2_pa_form_boundary_info(self._h, *[ctypes.byref(a) for a in v]))
+        return tuple(a.value for a in v)
+
+    def BoundaryQData(self, index: int) -> np.ndarray:
+        """pa_data of boundary integrator `index` [nbe][q1d^2] (MassIntegrator::AssemblePABoundary's
+        layout); zeros on the faces its marker excludes."""
+        nbe, _, _, q = self.BoundaryInfo()
+        out = np.empty((nbe, q * q), np.float64)
+        _check(_lib.ecm2_pa_form_get_boundary_qdata(self._h, index, _np_ptr(out), _stream()))
+        return out
+
     def Assemble(self, stream=None):
         if getattr(self, "_marked", False):  # the mesh's current attributes, as the reference reads them
             attr = np.ascontiguousarray(self.fes.mesh.GetAttributes())
@@ -813,6 +920,11 @@ _PAR_SIGS = {
                                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                               ctypes.c_int]),
     "ecm2_linear_form_assemble": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "ecm2_linear_form_set_boundary": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_int]),
+    "ecm2_linear_form_set_boundary_detj": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "ecm2_linear_form_add_boundary_integrator": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                                ctypes.c_void_p, ctypes.c_int]),
     "ecm2_linear_form_info": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_int)] * 5),
     "ecm2_linear_form_destroy": (None, [ctypes.c_void_p]),
 }
@@ -1206,6 +1318,14 @@ class DomainLFIntegrator:
         self.coeff = coeff
 
 
+class BoundaryLFIntegrator:
+    """BoundaryLFIntegrator(Q) (lininteg.hpp:200): (g, v) over boundary faces for a ConstantCoefficient or
+    a QuadratureCoefficient (CUDA float64 [nbe][q1d^2], boundary element order)."""
+
+    def __init__(self, coeff):
+        self.coeff = coeff
+
+
 def linear_form_default_q1d(order: int) -> int:
     """Points per direction of DomainLFIntegrator's default rule (order 2 p: p + 1)."""
     return _par_lib().ecm2_linear_form_default_q1d(order)
@@ -1272,6 +1392,39 @@ class LinearForm:
             self._marked = True
         _check(_lib.ecm2_linear_form_add_domain_integrator(self._h, kind, data, data2, params,
                                                            _np_ptr(mk) if mk is not None else None, n))
+
+    def SetBoundary(self, q1d: int = 0):
+        """Hand the form the space's boundary elements.  q1d = 0: BoundaryLFIntegrator's default rule,
+        (p + 1) // 2 + 1 points; p + 1 and p + 2 are supported too.  AddBoundaryIntegrator calls it."""
+        bm, at, bn = self.fes.boundary_map(), self.fes.mesh.GetBdrAttributes(), self.fes.mesh.boundary_nodes()
+        _check(_lib.ecm2_linear_form_set_boundary(self._h, bm.shape[0], _np_ptr(bm), _np_ptr(at), _np_ptr(bn), q1d))
+        p = self.fes.order
+        self._bdr_q1d = q1d if q1d > 0 else (p + 1) // 2 + 1
+
+    def SetBoundaryDetJ(self, detj):
+        """FaceGeometricFactors::detJ at the face rule (CUDA float64 [nbe][q1d^2]) instead of the corners."""
+        if getattr(self, "_bdr_q1d", None) is None:
+            self.SetBoundary()
+        _check_points(self, detj, ((),), self.fes.mesh.GetNBE(), self._bdr_q1d ** 2, flat_ok=True)
+        self._keep.append(detj)
+        _check(_lib.ecm2_linear_form_set_boundary_detj(self._h, _dev_ptr(detj)))
+
+    def AddBoundaryIntegrator(self, integ, bdr_marker=None):
+        """LinearForm::AddBoundaryIntegrator(new BoundaryLFIntegrator(g)[, bdr_marker]): bdr_marker 0 / 1
+        per boundary attribute.  Assembled after the domain integrators, in the order added."""
+        if getattr(self, "_bdr_q1d", None) is None:
+            self.SetBoundary()
+        c = integ.coeff
+        if isinstance(c, (ConstantCoefficient, QuadratureCoefficient)):
+            kind, data, _ = _integrator_args(c, self._keep, self.fes.mesh.GetNBE(), self._bdr_q1d ** 2, None)
+        else:
+            kind, data, _ = _integrator_args(c, self._keep, None, None, self.fes.ndofs)
+        mk, n = None, 0
+        if bdr_marker is not None:
+            mk = np.ascontiguousarray(bdr_marker, np.int32)
+            n = mk.size
+        _check(_lib.ecm2_linear_form_add_boundary_integrator(self._h, kind, data,
+                                                             _np_ptr(mk) if mk is not None else None, n))
 
     def Assemble(self, b, stream=None):
         """b (CUDA float64 [ndofs]) = the form's vector; the coefficients' tensors are read now."""

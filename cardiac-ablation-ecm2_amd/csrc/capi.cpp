@@ -281,6 +281,44 @@ int ecm2_mesh_element_order(const ecm2_mesh *m, int kind, int *perm)
    });
 }
 
+int ecm2_mesh_boundary_info(const ecm2_mesh *m, int *nbe)
+{
+   return guard([&] { NEED(m); NEED(nbe); *nbe = m->m.nbe(); });
+}
+
+int ecm2_mesh_get_boundary(const ecm2_mesh *m, int *verts, int *attr)
+{
+   return guard([&] {
+      NEED(m);
+      if (verts) { std::memcpy(verts, m->m.bdr.data(), m->m.bdr.size() * sizeof(int)); }
+      if (attr) { std::memcpy(attr, m->m.bdr_attr.data(), m->m.bdr_attr.size() * sizeof(int)); }
+   });
+}
+
+int ecm2_mesh_set_boundary_attributes(ecm2_mesh *m, const int *attr)
+{
+   return guard([&] {
+      NEED(m);
+      ECM2_VERIFY(m->m.nbe() == 0 || attr, ecm2::ERR_ARG, "null argument: attr");
+      for (int b = 0; b < m->m.nbe(); b++)
+      {
+         ECM2_VERIFY(attr[b] >= 1, ecm2::ERR_ARG, "boundary element " << b << " has attribute " << attr[b] << " < 1");
+      }
+      std::copy(attr, attr + m->m.nbe(), m->m.bdr_attr.begin());
+   });
+}
+
+int ecm2_mesh_get_boundary_nodes(const ecm2_mesh *m, double *out)
+{
+   return guard([&] {
+      NEED(m);
+      std::vector<double> n;
+      m->m.boundary_nodes(n);
+      ECM2_VERIFY(n.empty() || out, ecm2::ERR_ARG, "null argument: out");
+      if (!n.empty()) { std::memcpy(out, n.data(), n.size() * sizeof(double)); }
+   });
+}
+
 void ecm2_mesh_destroy(ecm2_mesh *m) { delete m; }
 
 // ---- space ----
@@ -343,6 +381,15 @@ int ecm2_h1space_dof_coords(const ecm2_h1space *s, const ecm2_mesh *m, double *o
    });
 }
 
+int ecm2_h1space_get_boundary_map(const ecm2_h1space *s, int *out)
+{
+   return guard([&] {
+      NEED(s);
+      ECM2_VERIFY(s->s.bdr_map.empty() || out, ecm2::ERR_ARG, "null argument: out");
+      if (!s->s.bdr_map.empty()) { std::memcpy(out, s->s.bdr_map.data(), s->s.bdr_map.size() * sizeof(int)); }
+   });
+}
+
 void ecm2_h1space_destroy(ecm2_h1space *s) { delete s; }
 
 // ---- PA form ----
@@ -388,6 +435,40 @@ int ecm2_pa_form_add_integrator_marked(ecm2_pa_form *f, int integrator, int coef
 int ecm2_pa_form_set_attributes(ecm2_pa_form *f, const int *attr)
 {
    return guard([&] { NEED(f); f->f->set_attributes(attr); });
+}
+
+int ecm2_pa_form_set_boundary(ecm2_pa_form *f, int nbe, const int *bdr_map, const int *bdr_attr,
+                              const double *bdr_nodes, int q1d)
+{
+   return guard([&] { NEED(f); f->f->set_boundary(nbe, bdr_map, bdr_attr, bdr_nodes, q1d); });
+}
+
+int ecm2_pa_form_set_boundary_detj(ecm2_pa_form *f, const double *detj)
+{
+   return guard([&] { NEED(f); f->f->set_boundary_detj(detj); });
+}
+
+int ecm2_pa_form_add_boundary_integrator(ecm2_pa_form *f, int integrator, int coeff_kind, const double *data,
+                                         const int *marker, int n_marker)
+{
+   return guard([&] {
+      NEED(f);
+      ecm2::CoeffDesc c;
+      c.kind = coeff_kind;
+      if (coeff_kind == ECM2_COEFF_CONSTANT) { c.value = data ? data[0] : 1.0; }
+      else if (coeff_kind == ECM2_COEFF_QUAD) { c.quad = data; }
+      f->f->add_boundary_integrator(integrator, c, marker, n_marker);
+   });
+}
+
+int ecm2_pa_form_get_boundary_qdata(ecm2_pa_form *f, int index, double *out, void *stream)
+{
+   return guard([&] { NEED(f); f->f->get_boundary_qdata(index, out, S(stream)); });
+}
+
+int ecm2_pa_form_boundary_info(const ecm2_pa_form *f, int *nbe, int *n_integrators, int *n_active, int *q1d)
+{
+   return guard([&] { NEED(f); f->f->boundary_info(nbe, n_integrators, n_active, q1d); });
 }
 
 int ecm2_pa_form_set_element_order(ecm2_pa_form *f, const int *perm)
@@ -1059,6 +1140,34 @@ int ecm2_linear_form_add_domain_integrator(ecm2_linear_form *lf, int coeff_kind,
       ECM2_VERIFY(coeff_kind == ECM2_COEFF_JOULE || data2 == nullptr, ecm2::ERR_ARG,
                   "data2 belongs to ECM2_COEFF_JOULE alone");
       lf->f.add_domain_integrator(c, marker, n_marker);
+   });
+}
+
+int ecm2_linear_form_set_boundary(ecm2_linear_form *lf, int nbe, const int *bdr_map, const int *bdr_attr,
+                                  const double *bdr_nodes, int q1d)
+{
+   return guard([&] { NEED(lf); lf->f.set_boundary(nbe, bdr_map, bdr_attr, bdr_nodes, q1d); });
+}
+
+int ecm2_linear_form_set_boundary_detj(ecm2_linear_form *lf, const double *detj)
+{
+   return guard([&] { NEED(lf); lf->f.set_boundary_detj(detj); });
+}
+
+int ecm2_linear_form_add_boundary_integrator(ecm2_linear_form *lf, int coeff_kind, const double *data,
+                                             const int *marker, int n_marker)
+{
+   return guard([&] {
+      NEED(lf);
+      ecm2::SourceDesc c;
+      c.kind = coeff_kind;
+      if (coeff_kind == ECM2_COEFF_CONSTANT)
+      {
+         NEED(data);
+         c.value = data[0];
+      }
+      else if (coeff_kind == ECM2_COEFF_QUAD) { c.quad = data; }
+      lf->f.add_boundary_integrator(c, marker, n_marker);
    });
 }
 

@@ -494,6 +494,41 @@ struct LFormArgs
 bool has_lform(int D, int Q);
 void lform_element_vectors(int D, int Q, const LFormArgs &a, const Basis1D &b, hipStream_t s);
 
+// ---- boundary faces (k_bdr.hip) ----
+// The face terms of a Robin condition over a compacted list of n boundary quads (`faces`: their
+// boundary element indices, ascending): MassIntegrator::AssemblePABoundary + the 2D mass apply and
+// diagonal (bilininteg_mass_pa.cpp:81-169) and BoundaryLFIntegrator (lininteg_boundary.cpp:74-153).
+// Face data are [n][q1d^2] / [n][d1d^2], lexicographic in the quad's frame (x fastest).
+struct BdrSetupArgs
+{
+   int n = 0, q1d = 0;
+   const int *faces = nullptr;      // device [n]
+   const double *nodes = nullptr;   // device [nbe][3][4] lexicographic corners, or
+   const double *detj = nullptr;    // device [nbe][q1d^2] (FaceGeometricFactors::detJ); exactly one
+   const double *wq = nullptr;      // device [q1d^2] tensor weights
+   const double *qpts = nullptr;    // device [q1d] Gauss-Legendre points (corner geometry)
+   double value = 1.0;              // the coefficient: a constant, or
+   const double *quad = nullptr;    // device [nbe][q1d^2] per-point values
+   const double *wf = nullptr;      // device [n] marker weights (0 / 1)
+   double *qd = nullptr;            // device [n][q1d^2]
+   bool accumulate = false;         // qd += (the later integrators of a form), else qd =
+};
+// qd[f][q] (+)= W_q c(q, f) detJ(q, f) w_f -- pa_data with the marker folded in
+void bdr_setup_qdata(const BdrSetupArgs &a, hipStream_t s);
+// (D1D, Q1D) of the face mass apply: p = 1..4 with p + 1 or p + 2 points
+bool has_bdr_apply(int D, int Q);
+// yf[f] = B^T (qd[f] o (B x_f)), x_f gathered through bmap ([nbe][d1d^2]); Bdev: device [Q][D]
+// (B[q + Q d]); b: the same table as a kernel argument (thread-per-face kernels)
+void bdr_mass_apply(int D, int Q, int n, const int *faces, const int *bmap, const double *qd, const double *x,
+                    double *yf, const Basis1D &b, const double *Bdev, hipStream_t s);
+// yf[f][i] = sum_q T[q][i] qd[f][q], T = B (x) B (the face linear form, BLFEvalAssemble3D) or its
+// entrywise square (the face mass diagonal, DiagonalPAKernels dim 2); any D, Q <= MAX
+void bdr_transpose_apply(int D, int Q, int n, const double *qd, bool squared, double *yf, const double *Bdev,
+                         hipStream_t s);
+// y[dof[r]] += sum_{k in off[r] .. off[r + 1]} yf[idx[k]] in ascending k: one thread per boundary dof,
+// no atomics
+void bdr_add(int nrows, const int *dof, const int *off, const int *idx, const double *yf, double *y, hipStream_t s);
+
 // ---- ElementRestriction ----
 void restriction_mult(long n, int nd, const int *gmap_native, const double *x, double *xe,
                       hipStream_t s);

@@ -6,7 +6,7 @@ namespace ecm2
 {
 
 LinearForm::LinearForm(int ne, int order, int ndofs, const int *gather_map_host, int q1d)
-   : ne_(ne), ndofs_(ndofs)
+   : ne_(ne), order_(order), ndofs_(ndofs), bdr_(order, ndofs)
 {
    ECM2_VERIFY(ne >= 0 && ndofs >= 0, ERR_ARG, "negative sizes");
    ECM2_VERIFY(order >= 1 && order + 1 <= MAX_D1D, ERR_ARG, "unsupported order " << order);
@@ -70,6 +70,26 @@ void LinearForm::add_domain_integrator(const SourceDesc &c, const int *marker, i
    g.marker.assign(marker, marker ? marker + n_marker : marker);
 }
 
+void LinearForm::set_boundary(int nbe, const int *bdr_map_host, const int *bdr_attr_host, const double *bdr_nodes_host, int q1d)
+{
+   const int q = q1d > 0 ? q1d : default_bdr_q1d(order_);
+   ECM2_VERIFY(q == default_bdr_q1d(order_) || q == D_ || q == D_ + 1, ERR_UNSUPPORTED,
+               "boundary rule of " << q << " points (the default, p + 1 or p + 2)");
+   ECM2_VERIFY(bdr_.n_integrators() == 0, ERR_STATE, "set_boundary after a boundary integrator was added");
+   bdr_.set_boundary(nbe, bdr_map_host, bdr_attr_host, bdr_nodes_host, q);
+}
+
+void LinearForm::set_boundary_detj(const double *detj_device) { bdr_.set_detj(detj_device); }
+
+void LinearForm::add_boundary_integrator(const SourceDesc &c, const int *marker, int n_marker)
+{
+   BdrCoeff bc;
+   bc.kind = c.kind;
+   bc.value = c.value;
+   bc.quad = c.quad;
+   bdr_.add_integrator(bc, marker, n_marker);
+}
+
 void LinearForm::ensure_csr()
 {
    if (csr_off_.size() || ndofs_ == 0) { return; }
@@ -88,7 +108,9 @@ void LinearForm::assemble(double *b, hipStream_t s)
    if (ndofs_ == 0) { return; }
    if (integs_.empty() || ne_ == 0)
    {
+      // (a form with boundary integrators only still overwrites b)
       ECM2_HIP(hipMemsetAsync(b, 0, (size_t)ndofs_ * sizeof(double), s));
+      if (bdr_.n_integrators()) { bdr_.add_linear(b, s); }
       return;
    }
    // the markers of this assembly: 0 / 1 per element from the attributes (linearform_ext.cpp:49-61)
@@ -138,6 +160,8 @@ void LinearForm::assemble(double *b, hipStream_t s)
       kern::restriction_mult_transpose(ndofs_, ND_, csr_off_.data(), csr_idx_.data(), be_.data(), dst, s);
       if (k > 0) { kern::add_scaled(ndofs_, b, 1.0, bwork_.data(), b, s); }
    }
+   // the boundary integrators, after the domain ones (linearform_ext.cpp:70-111)
+   if (bdr_.n_integrators()) { bdr_.add_linear(b, s); }
 }
 
 } // namespace ecm2

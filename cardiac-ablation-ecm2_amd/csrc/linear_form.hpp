@@ -11,6 +11,7 @@
 // coefficients' device arrays and b are caller-owned; all work is enqueued on the caller's stream.
 #pragma once
 
+#include "bdr_term.hpp"
 #include "common.hpp"
 #include "fe.hpp"
 #include "kernels.hpp"
@@ -44,6 +45,10 @@ public:
    int d1d() const { return D_; }
    int q1d() const { return Q_; }
    int n_integrators() const { return (int)integs_.size(); }
+   int n_boundary_integrators() const { return bdr_.n_integrators(); }
+   // BoundaryLFIntegrator(Q, a = 1, b = 1): the rule of order a p + b (lininteg.hpp:200),
+   // (p + 1) / 2 + 1 Gauss-Legendre points per direction (2, 2, 3, 3 for p = 1..4)
+   static int default_bdr_q1d(int order) { return (order + 1) / 2 + 1; }
 
    // Geometry: lexicographic corners (host [ne][3][8]) or MFEM-layout Jacobians (device,
    // NQ x 3 x 3 x NE, valid for as long as the form is assembled); the last call wins.
@@ -54,9 +59,18 @@ public:
    // LinearForm::AddDomainIntegrator(lfi[, elem_marker]) (linearform.cpp): marker host [n_marker],
    // 0 / 1 per attribute, null = all elements
    void add_domain_integrator(const SourceDesc &c, const int *marker = nullptr, int n_marker = 0);
+   // Boundary integrators (LinearForm::AddBoundaryIntegrator(new BoundaryLFIntegrator(g), bdr_marker);
+   // LinearFormExtension::Assemble's boundary loop, linearform_ext.cpp:70-111; BLFEvalAssemble3D,
+   // lininteg_boundary.cpp:74-153): set_boundary takes PAForm::set_boundary's arguments, q1d <= 0
+   // selects default_bdr_q1d, and that, p + 1 and p + 2 points are supported.  The coefficient is a
+   // constant or per-point values (device [nbe][q1d^2], read at every assemble).
+   void set_boundary(int nbe, const int *bdr_map_host, const int *bdr_attr_host, const double *bdr_nodes_host, int q1d);
+   void set_boundary_detj(const double *detj_device);
+   void add_boundary_integrator(const SourceDesc &c, const int *marker = nullptr, int n_marker = 0);
    // b = sum over the integrators, in the order they were added: each one's element vectors, then
    // the CSR transpose -- the first stores, the later ones add (linearform_ext.cpp:64-67).  The
-   // coefficients' device arrays are read here, every time.
+   // coefficients' device arrays are read here, every time.  The boundary integrators follow the domain
+   // ones, each added through the boundary dofs' CSR in ascending face order (no atomics).
    void assemble(double *b, hipStream_t s);
 
 private:
@@ -70,7 +84,8 @@ private:
    };
    void ensure_csr();
 
-   int ne_, ndofs_, D_, Q_, ND_, NQ_;
+   int ne_, order_, ndofs_, D_, Q_, ND_, NQ_;
+   BoundaryTerm bdr_;
    DofToQuad maps_;
    Basis1D basis_;
    QPts qp_ = {};

@@ -129,6 +129,26 @@ HexMesh HexMesh::cartesian(int nx, int ny, int nz, double sx, double sy, double 
       ind[4] = vtx(x, y, z + 1); ind[5] = vtx(x + 1, y, z + 1);
       ind[6] = vtx(x + 1, y + 1, z + 1); ind[7] = vtx(x, y + 1, z + 1);
    }
+   // Boundary elements (mesh.cpp:3815-3949): bottom 1, top 6, left 5, right 3, front 2, back 4, in
+   // that order and with those vertex orders; independent of the element ordering.
+   m.bdr.reserve(8 * ((size_t)nx * ny + (size_t)ny * nz + (size_t)nx * nz));
+   auto quad = [&](int a, int b, int c, int d, int at) {
+      const int q[4] = {a, b, c, d};
+      m.bdr.insert(m.bdr.end(), q, q + 4);
+      m.bdr_attr.push_back(at);
+   };
+   for (int y = 0; y < ny; y++)
+      for (int x = 0; x < nx; x++) { quad(vtx(x, y, 0), vtx(x, y + 1, 0), vtx(x + 1, y + 1, 0), vtx(x + 1, y, 0), 1); }
+   for (int y = 0; y < ny; y++)
+      for (int x = 0; x < nx; x++) { quad(vtx(x, y, nz), vtx(x + 1, y, nz), vtx(x + 1, y + 1, nz), vtx(x, y + 1, nz), 6); }
+   for (int z = 0; z < nz; z++)
+      for (int y = 0; y < ny; y++) { quad(vtx(0, y, z), vtx(0, y, z + 1), vtx(0, y + 1, z + 1), vtx(0, y + 1, z), 5); }
+   for (int z = 0; z < nz; z++)
+      for (int y = 0; y < ny; y++) { quad(vtx(nx, y, z), vtx(nx, y + 1, z), vtx(nx, y + 1, z + 1), vtx(nx, y, z + 1), 3); }
+   for (int x = 0; x < nx; x++)
+      for (int z = 0; z < nz; z++) { quad(vtx(x, 0, z), vtx(x + 1, 0, z), vtx(x + 1, 0, z + 1), vtx(x, 0, z + 1), 2); }
+   for (int x = 0; x < nx; x++)
+      for (int z = 0; z < nz; z++) { quad(vtx(x, ny, z), vtx(x, ny, z + 1), vtx(x + 1, ny, z + 1), vtx(x + 1, ny, z), 4); }
    return m;
 }
 
@@ -188,6 +208,7 @@ HexMesh HexMesh::read(const std::string &path)
                "unsupported mesh format header '" << line << "'");
    HexMesh m;
    int dim = 0;
+   bool have_bdr = false;
    while (next_content_line(in, line))
    {
       if (line == "dimension")
@@ -215,10 +236,24 @@ HexMesh HexMesh::read(const std::string &path)
       }
       else if (line == "boundary")
       {
-         // The boundary is re-derived from the element faces (conforming meshes).
+         // boundary elements: attribute, geometry type (3 = SQUARE only), 4 vertices
          next_content_line(in, line);
          const int nb = std::stoi(line);
-         for (int b = 0; b < nb; b++) { next_content_line(in, line); }
+         ECM2_VERIFY(nb >= 0, ERR_IO, "negative boundary element count");
+         have_bdr = true;
+         m.bdr.resize((size_t)nb * 4);
+         m.bdr_attr.resize(nb);
+         for (int b = 0; b < nb; b++)
+         {
+            ECM2_VERIFY(next_content_line(in, line), ERR_IO, "truncated boundary");
+            std::istringstream ls(line);
+            int a = 0, g = -1;
+            ls >> a >> g;
+            ECM2_VERIFY(g == 3, ERR_UNSUPPORTED, "boundary element geometry " << g << " (only quadrilateral = 3)");
+            m.bdr_attr[b] = a;
+            for (int k = 0; k < 4; k++) { ls >> m.bdr[4 * (size_t)b + k]; }
+            ECM2_VERIFY(!ls.fail(), ERR_IO, "malformed boundary element " << b);
+         }
       }
       else if (line == "vertices")
       {
@@ -242,6 +277,8 @@ HexMesh HexMesh::read(const std::string &path)
    }
    ECM2_VERIFY(m.ne > 0 && m.nv > 0, ERR_IO, "mesh has no elements or vertices");
    for (int v : m.elem) { ECM2_VERIFY(v >= 0 && v < m.nv, ERR_IO, "vertex index out of range"); }
+   for (int v : m.bdr) { ECM2_VERIFY(v >= 0 && v < m.nv, ERR_IO, "boundary vertex index out of range"); }
+   if (!have_bdr) { m.generate_boundary(); }
    return m;
 }
 
@@ -362,6 +399,62 @@ void HexMesh::refine_uniform()
          nattr[(size_t)i * 8 + k] = attr[i];
       }
    }
+   // Boundary elements (mesh.cpp:10716-10764): quad i -> children 4i..4i+3 with the parent's
+   // attribute, from its vertices, its edges' midpoints (bel_to_edge: v0v1, v1v2, v2v3, v3v0) and
+   // its face's centre.  Only entities whose vertices all lie on boundary quads are looked up.
+   const int nb = nbe();
+   std::vector<int> nbdr((size_t)nb * 16), nbattr((size_t)nb * 4);
+   if (nb)
+   {
+      std::vector<char> onb(nv, 0);
+      for (int v : bdr) { onb[v] = 1; }
+      std::unordered_map<uint64_t, int> edge_of;
+      std::unordered_map<Key3, int, Key3Hash> face_of;
+      auto ekey = [](int a, int b) { return ((uint64_t)(uint32_t)std::min(a, b) << 32) | (uint32_t)std::max(a, b); };
+      auto fkey = [](const int *q) {
+         int srt[4] = {q[0], q[1], q[2], q[3]};
+         std::sort(srt, srt + 4);
+         return Key3{srt[0], srt[1], srt[2]};
+      };
+      for (int i = 0; i < ne; i++)
+      {
+         const int *v = &elem[8 * (size_t)i];
+         for (int k = 0; k < 12; k++)
+         {
+            const int a = v[kHexEdges[k][0]], b = v[kHexEdges[k][1]];
+            if (onb[a] && onb[b]) { edge_of.emplace(ekey(a, b), t.elem_edges[(size_t)i * 12 + k]); }
+         }
+         for (int k = 0; k < 6; k++)
+         {
+            int q[4];
+            bool all = true;
+            for (int r = 0; r < 4; r++) { q[r] = v[kHexFaceVert[k][r]]; all = all && onb[q[r]]; }
+            if (all) { face_of.emplace(fkey(q), t.elem_faces[(size_t)i * 6 + k]); }
+         }
+      }
+      for (int i = 0; i < nb; i++)
+      {
+         const int *v = &bdr[4 * (size_t)i];
+         int e[4];
+         for (int k = 0; k < 4; k++)
+         {
+            auto it = edge_of.find(ekey(v[k], v[(k + 1) % 4]));
+            ECM2_VERIFY(it != edge_of.end(), ERR_ARG, "boundary element " << i << " has an edge no element has");
+            e[k] = oedge + it->second;
+         }
+         auto fit = face_of.find(fkey(v));
+         ECM2_VERIFY(fit != face_of.end(), ERR_ARG, "boundary element " << i << " is not a face of an element");
+         const int qf = oface + fit->second;
+         const int kids[4][4] = {{v[0], e[0], qf, e[3]}, {e[0], v[1], e[1], qf}, {qf, e[1], v[2], e[2]}, {e[3], qf, e[2], v[3]}};
+         for (int k = 0; k < 4; k++)
+         {
+            std::copy(kids[k], kids[k] + 4, &nbdr[((size_t)i * 4 + k) * 4]);
+            nbattr[(size_t)i * 4 + k] = bdr_attr[i];
+         }
+      }
+   }
+   bdr.swap(nbdr);
+   bdr_attr.swap(nbattr);
    vert.swap(nvert);
    elem.swap(nelem);
    attr.swap(nattr);
@@ -472,6 +565,99 @@ void HexMesh::element_nodes(std::vector<double> &out) const
          }
 }
 
+void HexMesh::boundary_nodes(std::vector<double> &out) const
+{
+   static const int lex[4] = {0, 1, 3, 2};  // lexicographic corner a = ax + 2 ay <- quad vertex
+   const int nb = nbe();
+   out.resize((size_t)nb * 12);
+   for (int b = 0; b < nb; b++)
+      for (int c = 0; c < 3; c++)
+         for (int a = 0; a < 4; a++) { out[(size_t)b * 12 + c * 4 + a] = vert[3 * (size_t)bdr[4 * (size_t)b + lex[a]] + c]; }
+}
+
+void HexMesh::generate_boundary()
+{
+   const HexTopology t = HexTopology::build(*this);
+   bdr.clear();
+   bdr_attr.clear();
+   for (int f = 0; f < t.nfaces; f++)
+   {
+      if (t.face_count[f] != 1) { continue; }
+      bdr.insert(bdr.end(), &t.face_vert[(size_t)f * 4], &t.face_vert[(size_t)f * 4] + 4);
+      bdr_attr.push_back(1);
+   }
+}
+
+namespace
+{
+// H1Space::bdr_map: every boundary quad's element and local face (the element face with the same
+// vertex set), then the lattice points of that face walked in the quad's frame.
+void build_bdr_map(const HexMesh &m, H1Space &s)
+{
+   static const int L[8][3] = {{0, 0, 0}, {1, 0, 0}, {1, 1, 0}, {0, 1, 0}, {0, 0, 1}, {1, 0, 1}, {1, 1, 1}, {0, 1, 1}};
+   const int nb = m.nbe(), p = s.order, D = p + 1;
+   s.bdr_map.assign((size_t)nb * D * D, -1);
+   if (!nb) { return; }
+   auto fkey = [](const int *q) {
+      int srt[4] = {q[0], q[1], q[2], q[3]};
+      std::sort(srt, srt + 4);
+      return Key3{srt[0], srt[1], srt[2]};
+   };
+   std::vector<char> onb(m.nv, 0);
+   for (int v : m.bdr) { onb[v] = 1; }
+   std::unordered_map<Key3, int, Key3Hash> elem_of;  // vertex set -> 6 e + local face (a face of one element)
+   elem_of.reserve((size_t)nb * 2);
+   for (int b = 0; b < nb; b++) { elem_of.emplace(fkey(&m.bdr[4 * (size_t)b]), -1); }
+   for (int e = 0; e < m.ne; e++)
+   {
+      const int *v = &m.elem[8 * (size_t)e];
+      for (int k = 0; k < 6; k++)
+      {
+         int q[4];
+         bool all = true;
+         for (int r = 0; r < 4; r++) { q[r] = v[kHexFaceVert[k][r]]; all = all && onb[q[r]]; }
+         if (!all) { continue; }
+         auto it = elem_of.find(fkey(q));
+         if (it == elem_of.end()) { continue; }
+         ECM2_VERIFY(it->second < 0, ERR_ARG, "a boundary element lies on an interior face (elements "
+                                                 << it->second / 6 << " and " << e << ")");
+         it->second = 6 * e + k;
+      }
+   }
+   for (int b = 0; b < nb; b++)
+   {
+      const int *bv = &m.bdr[4 * (size_t)b];
+      const int ek = elem_of[fkey(bv)];
+      ECM2_VERIFY(ek >= 0, ERR_ARG, "boundary element " << b << " is not a face of an element");
+      const int e = ek / 6;
+      const int *v = &m.elem[8 * (size_t)e];
+      int n[4];
+      for (int r = 0; r < 4; r++)
+      {
+         n[r] = -1;
+         for (int c = 0; c < 8; c++) { if (v[c] == bv[r]) { n[r] = c; } }
+         ECM2_VERIFY(n[r] >= 0, ERR_ARG, "boundary element " << b << " is not a face of element " << e);
+      }
+      int d1 = 0, d3 = 0, d13 = 0;
+      for (int c = 0; c < 3; c++)
+      {
+         d1 += L[n[1]][c] != L[n[0]][c];
+         d3 += L[n[3]][c] != L[n[0]][c];
+         d13 += L[n[1]][c] != L[n[3]][c];
+      }
+      ECM2_VERIFY(d1 == 1 && d3 == 1 && d13 == 2, ERR_ARG, "boundary element " << b << ": vertices are not in cyclic order");
+      // lattice point of (a, b): l0 + a (l1 - l0) + b (l3 - l0), corners scaled by p
+      for (int j = 0; j < D; j++)
+         for (int i = 0; i < D; i++)
+         {
+            int l[3];
+            for (int c = 0; c < 3; c++) { l[c] = p * L[n[0]][c] + i * (L[n[1]][c] - L[n[0]][c]) + j * (L[n[3]][c] - L[n[0]][c]); }
+            const int g = s.gather_map[(size_t)e * s.nd + (l[2] * D + l[1]) * D + l[0]];
+            s.bdr_map[(size_t)b * D * D + j * D + i] = g >= 0 ? g : -1 - g;
+         }
+   }
+}
+} // namespace
 
 H1Space H1Space::build(const HexMesh &m, int order, int numbering)
 {
@@ -510,6 +696,7 @@ H1Space H1Space::build(const HexMesh &m, int order, int numbering)
                   s.bdr_dofs.push_back((int)(I + NX * (J + NY * K)));
                }
             }
+      build_bdr_map(m, s);
       return s;
    }
    ECM2_VERIFY(numbering == NUMBERING_ENTITY, ERR_ARG, "unknown numbering " << numbering);
@@ -624,6 +811,7 @@ H1Space H1Space::build(const HexMesh &m, int order, int numbering)
       }
    }
    for (int d = 0; d < s.ndofs; d++) { if (on_bdr[d]) { s.bdr_dofs.push_back(d); } }
+   build_bdr_map(m, s);
    return s;
 }
 

@@ -26,6 +26,14 @@ struct HexMesh
    std::vector<double> vert;   // [nv][3]
    std::vector<int> elem;      // [ne][8] native order
    std::vector<int> attr;      // [ne]
+   // Boundary elements (quadrilaterals, geometry type 3): vertex ids in the quad's native order and
+   // the boundary attribute.  Mesh::Make3D fills them side by side (mesh.cpp:3815-3949), the v1.0
+   // reader takes the file's `boundary` section, a file without one gets
+   // Mesh::GenerateBoundaryElements (mesh.cpp:2453-2500), refinement splits each in four
+   // (mesh.cpp:10716-10764).
+   int nbe() const { return (int)bdr_attr.size(); }
+   std::vector<int> bdr;       // [nbe][4]
+   std::vector<int> bdr_attr;  // [nbe]
    // Cartesian provenance (for the structured numbering); nx = 0 when unstructured.  lex[e] =
    // ex + nx (ey + ny ez), the lattice position of element e (empty: lexicographic order).
    int nx = 0, ny = 0, nz = 0;
@@ -40,6 +48,11 @@ struct HexMesh
    void refine_uniform();
    // Corner coordinates in lexicographic order: out[e][c][a] (a = lex corner).
    void element_nodes(std::vector<double> &out) const;
+   // Corner coordinates of the boundary quads in the quad's lexicographic frame (xi: v0 -> v1,
+   // eta: v0 -> v3): out[b][c][a], a = 0..3 <-> v0, v1, v3, v2.
+   void boundary_nodes(std::vector<double> &out) const;
+   // Mesh::GenerateBoundaryElements: the faces with one element, in face order, attribute 1
+   void generate_boundary();
 };
 
 enum ElementOrder : int
@@ -86,6 +99,12 @@ struct H1Space
    int numbering = NUMBERING_ENTITY;
    std::vector<int> gather_map;   // [ne][nd] lexicographic, MFEM gather_map semantics
    std::vector<int> bdr_dofs;     // sorted dofs on boundary faces (ess_tdof_list for ess_bdr = all)
+   // Dofs of every boundary element, [nbe][(p+1)^2], lexicographic in the quad's own frame (xi runs
+   // v0 -> v1, eta runs v0 -> v3: what HexMesh::boundary_nodes gives the geometry in), read from the
+   // adjacent element's row of gather_map -- the boundary FaceRestriction's map
+   // (fem/restriction.cpp, FaceType::Boundary) up to the frame, which the face integrals do not
+   // depend on as long as dofs and corners share it.
+   std::vector<int> bdr_map;
 
    static H1Space build(const HexMesh &m, int order, int numbering);
    // Physical coordinates of every dof (from the element trilinear map at GLL nodes).

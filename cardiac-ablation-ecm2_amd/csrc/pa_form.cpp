@@ -22,7 +22,7 @@ void require_device()
 }
 
 PAForm::PAForm(int ne, int order, int ndofs, const int *gather_map_host, int q1d, int n_owned)
-   : ne_(ne), order_(order), ndofs_(ndofs), n_owned_(n_owned < 0 ? ndofs : n_owned)
+   : ne_(ne), order_(order), ndofs_(ndofs), n_owned_(n_owned < 0 ? ndofs : n_owned), bdr_(order, ndofs)
 {
    ECM2_VERIFY(n_owned_ <= ndofs, ERR_ARG, "n_owned > ndofs");
    ECM2_VERIFY(ne >= 0 && ndofs >= 0, ERR_ARG, "negative sizes");
@@ -170,6 +170,49 @@ void PAForm::add_integrator(int kind, const CoeffDesc &c, const int *marker, int
    assembled_ = false;
 }
 
+void PAForm::set_boundary(int nbe, const int *bdr_map_host, const int *bdr_attr_host, const double *bdr_nodes_host, int q1d)
+{
+   ECM2_VERIFY(n_owned_ == ndofs_, ERR_UNSUPPORTED, "a distributed local form has no boundary integrators");
+   const int q = q1d > 0 ? q1d : D_;  // MassIntegrator::GetRule on the boundary quad: p + 1 points
+   ECM2_VERIFY(q == D_ || q == D_ + 1, ERR_UNSUPPORTED, "boundary rule of " << q << " points (p + 1 or p + 2)");
+   ECM2_VERIFY(kern::has_bdr_apply(D_, q), ERR_UNSUPPORTED, "no face mass kernel for order " << order_);
+   ECM2_VERIFY(bdr_.n_integrators() == 0, ERR_STATE, "set_boundary after a boundary integrator was added");
+   bdr_.set_boundary(nbe, bdr_map_host, bdr_attr_host, bdr_nodes_host, q);
+   assembled_ = false;
+}
+
+void PAForm::set_boundary_detj(const double *detj_device)
+{
+   bdr_.set_detj(detj_device);
+   assembled_ = false;
+}
+
+void PAForm::add_boundary_integrator(int kind, const CoeffDesc &c, const int *marker, int n_marker)
+{
+   ECM2_VERIFY(kind == INTEG_MASS || kind == INTEG_DIFFUSION, ERR_ARG, "unknown integrator " << kind);
+   ECM2_VERIFY(kind == INTEG_MASS, ERR_UNSUPPORTED, "only a MassIntegrator is supported on the boundary");
+   BdrCoeff bc;
+   bc.kind = c.kind;
+   bc.value = c.value;
+   bc.quad = c.quad;
+   bdr_.add_integrator(bc, marker, n_marker);
+   assembled_ = false;
+}
+
+void PAForm::get_boundary_qdata(int index, double *out_host, hipStream_t s)
+{
+   ECM2_VERIFY(assembled_, ERR_STATE, "get_boundary_qdata before Assemble");
+   bdr_.get_qdata(index, out_host, s);
+}
+
+void PAForm::boundary_info(int *nbe, int *n_integrators, int *n_active, int *q1d) const
+{
+   if (nbe) { *nbe = bdr_.nbe(); }
+   if (n_integrators) { *n_integrators = bdr_.n_integrators(); }
+   if (n_active) { *n_active = bdr_.n_active(); }
+   if (q1d) { *q1d = bdr_.q1d(); }
+}
+
 void PAForm::set_element_order(const int *perm)
 {
    std::vector<int> seen(ne_, 0);
@@ -225,6 +268,7 @@ void PAForm::assemble(hipStream_t s)
    setup_qdata(s);
    setup_marker_diagonal(s);
    build_launch_args();
+   if (bdr_.has_boundary()) { bdr_.assemble_mass(s); }  // face qdata and the add pass's CSR
    assembled_ = true;
    gen_++;
 }
@@ -581,6 +625,14 @@ void PAForm::mult(const double *x, double *y, hipStream_t s)
    ECM2_VERIFY(assembled_, ERR_STATE, "Mult before Assemble");
    ECM2_VERIFY(ndofs_ == 0 || (x && y), ERR_ARG, "null vector");
    if (ndofs_ == 0) { return; }
+   mult_volume(x, y, s);
+   // the boundary block of PABilinearFormExtension::Mult (bilinearform_ext.cpp:625-675), after the
+   // volume result is complete (partial scatter: after finish_shared), whatever kernel computed it
+   if (has_boundary_integrators()) { bdr_.add_mult(x, y, s); }
+}
+
+void PAForm::mult_volume(const double *x, double *y, hipStream_t s)
+{
    const bool m = have_mass_, d = have_diff_;
    if (resolved_mode_ == KERNEL_UNFUSED)
    {
@@ -626,7 +678,9 @@ int PAForm::energy_parts() const
    // cost -- profiles/r6/ab_brick_energy.txt.)
    const bool ts = assembled_ && use_partials() && resolved_mode_ == KERNEL_TPE && layout_.kind == QLAYOUT_AFFINE &&
                    layout_.tsnap && have_diff_ && D_ == 3 && Q_ == 4;
-   return ts && ndofs_ > 0 ? (layout_.nblk() + 3) / 4 : 0;
+   // (a boundary integrator: the folded sum would miss d^T H d of the face term, so the caller runs
+   // the dot pass over the complete Mult)
+   return ts && ndofs_ > 0 && !has_boundary_integrators() ? (layout_.nblk() + 3) / 4 : 0;
 }
 
 void PAForm::mult_energy(const double *x, double *y, double *en, hipStream_t s)
@@ -780,6 +834,8 @@ void PAForm::assemble_diagonal(double *diag, hipStream_t s)
       return;
    }
    assemble_diagonal_uncached(diag, s);
+   // the boundary block (bilinearform_ext.cpp:441-452), added to the complete volume diagonal
+   if (has_boundary_integrators()) { bdr_.add_diagonal(diag, s); }
    diag_cache_.resize(ndofs_);
    ECM2_HIP(hipMemcpyAsync(diag_cache_.data(), diag, diag_cache_.bytes(), hipMemcpyDeviceToDevice, s));
    diag_gen_ = gen_;

@@ -21,6 +21,7 @@
 // and the snapshot, and ApplyArgs, filled per call (vectors, block range, the qdata to read).
 #pragma once
 
+#include "bdr_term.hpp"
 #include "common.hpp"
 #include "fe.hpp"
 #include "kernels.hpp"
@@ -133,6 +134,23 @@ public:
    void add_integrator(int kind, const CoeffDesc &c, const int *marker = nullptr, int n_marker = 0);
    // element attributes (host [ne], caller element order), as Mesh::GetAttribute
    void set_attributes(const int *attr_host);
+   // Boundary integrators (BilinearForm::AddBoundaryIntegrator(new MassIntegrator(h), bdr_marker):
+   // the Robin term; PABilinearFormExtension's boundary blocks, bilinearform_ext.cpp:300-328, 441-452,
+   // 625-675; MassIntegrator::AssemblePABoundary, bilininteg_mass_pa.cpp:81-125).  set_boundary: the
+   // boundary elements' dofs (host [nbe][(p+1)^2]), attributes (host [nbe]) and lexicographic corners
+   // (host [nbe][3][4], the frame of the dof rows); q1d <= 0 selects MassIntegrator::GetRule's p + 1
+   // points (order 2p + 1 on a bilinear quad), p + 1 and p + 2 are supported.  A distributed local
+   // form (n_owned < ndofs) has no boundary terms.  set_boundary_detj: FaceGeometricFactors::detJ
+   // (device [nbe][q1d^2], valid until assemble()) instead of the corners.  All boundary integrators
+   // share the rule; their qdata are summed at assemble() and one face apply, run after the volume
+   // result is complete, serves Mult in every kernel mode.
+   void set_boundary(int nbe, const int *bdr_map_host, const int *bdr_attr_host, const double *bdr_nodes_host, int q1d);
+   void set_boundary_detj(const double *detj_device);
+   void add_boundary_integrator(int kind, const CoeffDesc &c, const int *marker = nullptr, int n_marker = 0);
+   // pa_data of boundary integrator `index` (host [nbe][q1d^2]; zeros on faces its marker excludes)
+   void get_boundary_qdata(int index, double *out_host, hipStream_t s);
+   void boundary_info(int *nbe, int *n_integrators, int *n_active, int *q1d) const;
+   bool has_boundary_integrators() const { return bdr_.n_integrators() > 0; }
    void set_kernel(int mode);
    void set_scatter(int mode);
    int scatter() const { return scatter_; }
@@ -152,7 +170,8 @@ public:
    // The Mult with its energy x^T A x folded in (CGSolver's den = (A d, d), solvers.cpp:993, without
    // a dot pass over the vectors): energy_parts() partials (one per workgroup of the single apply
    // launch, summed in a fixed order by the caller) -- or 0 when this form's kernel does not fold it
-   // (only the coefficient-snapshot kernel k_apply_tpe_ts does; the caller then runs the dot).
+   // (only the coefficient-snapshot kernel k_apply_tpe_ts does, and not for a form with a boundary
+   // integrator, whose face term the folded sum would miss; the caller then runs the dot).
    int energy_parts() const;
    void mult_energy(const double *x, double *y, double *en, hipStream_t s);
    bool assembled() const { return assembled_; }
@@ -204,6 +223,8 @@ private:
    QData qdata() const { return {qd_diff_.data(), qd_mass_.data()}; }
    void ensure_csr();
    void ensure_work(hipStream_t s);
+   // the volume part of Mult (y overwritten); mult adds the boundary term after it
+   void mult_volume(const double *x, double *y, hipStream_t s);
    // a setter that feeds build_tpe_plan / build_line_plan drops that plan: Assemble rebuilds it
    void invalidate_plans(bool tpe, bool line);
    // assemble()'s steps, in order: kernel mode and qdata layout; the fused kernel's scatter plan
@@ -238,6 +259,7 @@ private:
    void expand_compressed(QData q, DeviceArray<double> &fd, DeviceArray<double> &fm, hipStream_t s) const;
 
    int ne_, order_, ndofs_, n_owned_, D_, Q_, ND_, NQ_;
+   BoundaryTerm bdr_;               // boundary integrators (empty unless set_boundary was called)
    DofToQuad maps_;
    QPts qp_ = {};                   // maps_.qpts as a kernel argument
    Basis1D basis_, basis1_;

@@ -120,6 +120,20 @@ int ecm2_mesh_get_attributes(const ecm2_mesh *m, int *out);
 int ecm2_mesh_set_attributes(ecm2_mesh *m, const int *in);
 /* Lexicographic corner coordinates, host out[ne][3][8]. */
 int ecm2_mesh_get_element_nodes(const ecm2_mesh *m, double *out);
+/* Boundary elements (Mesh::GetNBE / GetBdrElementVertices / GetBdrAttribute): quadrilaterals.
+ * Mesh::Make3D's six sides in its order (mesh/mesh.cpp:3815-3949: attributes 1 bottom, 6 top, 5 left,
+ * 3 right, 2 front, 4 back), the `boundary` section of a v1.0 file (geometry type 3 only, anything
+ * else is ECM2_ERR_UNSUPPORTED), Mesh::GenerateBoundaryElements (mesh.cpp:2453-2500: the faces with
+ * one element, attribute 1) for a file without one; refinement gives quad i the children
+ * 4i..4i+3 with its attribute (mesh.cpp:10716-10764). */
+int ecm2_mesh_boundary_info(const ecm2_mesh *m, int *nbe);
+int ecm2_mesh_get_boundary(const ecm2_mesh *m, int *verts /* host [nbe][4], the quad's order */,
+                           int *attr /* host [nbe] */);
+int ecm2_mesh_set_boundary_attributes(ecm2_mesh *m, const int *attr /* host [nbe], every one >= 1 */);
+/* Corners of the boundary quads in the quad's lexicographic frame (xi runs v0 -> v1, eta runs
+ * v0 -> v3: the corners v0, v1, v3, v2), host out[nbe][3][4] -- the frame of
+ * ecm2_h1space_get_boundary_map. */
+int ecm2_mesh_get_boundary_nodes(const ecm2_mesh *m, double *out);
 /* Physical coordinates of the Gauss-Legendre quadrature points of every element, host
  * out[ne][q1d^3][3] (q lexicographic, qx fastest): the points a FunctionCoefficient is
  * projected at (Coefficient::Project, fem/coefficient.cpp:52-70). */
@@ -147,6 +161,10 @@ int ecm2_h1space_get_gather_map(const ecm2_h1space *s, int *out /* host [ne][nd]
 int ecm2_h1space_element_order(const ecm2_h1space *s, int *perm);
 int ecm2_h1space_boundary_dofs(const ecm2_h1space *s, int *out, int *count);
 int ecm2_h1space_dof_coords(const ecm2_h1space *s, const ecm2_mesh *m, double *out /* host [ndofs][3] */);
+/* The dofs of every boundary element, host out[nbe][(order+1)^2], lexicographic in the quad's own
+ * frame (see ecm2_mesh_get_boundary_nodes), taken from the adjacent element's row of the gather
+ * map: the boundary FaceRestriction's map (bilinearform_ext.cpp:300-328) up to the frame. */
+int ecm2_h1space_get_boundary_map(const ecm2_h1space *s, int *out);
 void ecm2_h1space_destroy(ecm2_h1space *s);
 
 /* ------------------------------------------------------------------------ */
@@ -231,6 +249,42 @@ int ecm2_pa_form_add_integrator_marked(ecm2_pa_form *f, int integrator, int coef
                                        const double *params, const int *marker, int n_marker);
 /* Element attributes of the form's elements (the mesh's, host [ne], caller element order). */
 int ecm2_pa_form_set_attributes(ecm2_pa_form *f, const int *attr);
+/* Robin boundaries: BilinearForm::AddBoundaryIntegrator(new MassIntegrator(h)[, bdr_marker]) at
+ * AssemblyLevel::PARTIAL.
+ *   MassIntegrator::AssemblePABoundary (fem/integ/bilininteg_mass_pa.cpp:81-125): pa_data(q, f) =
+ *     W_q c detJ_face(q, f) over the boundary faces, dim = 2, rule MassIntegrator::GetRule on the
+ *     boundary quad (fem/bilininteg.cpp:1450-1462; order 2p + 1, OrderW = 1, fem/eltrans.cpp:493-507):
+ *     p + 1 Gauss-Legendre points per direction;
+ *   the 2D mass apply B^T D B and the 2D diagonal (bilininteg_mass_pa.cpp:127-169);
+ *   PABilinearFormExtension (fem/bilinearform_ext.cpp): setup :300-328, :354; Mult's boundary block
+ *     :625-675 (bdr_face_restrict_lex->Mult, AddMultWithMarkers over bdr_face_attributes :807-847,
+ *     AddMultTransposeInPlace); AssembleDiagonal's boundary block :441-452;
+ *   FaceGeometricFactors DETERMINANTS (mesh/mesh.cpp:15275-15334): |dx/dxi x dx/deta|.
+ * set_boundary: bdr_map host [nbe][(order+1)^2] (the boundary FaceRestriction's map, e.g.
+ * ecm2_h1space_get_boundary_map), bdr_attr host [nbe] (GetBdrFaceAttributes), bdr_nodes host
+ * [nbe][3][4] lexicographic corners in the frame of bdr_map's rows (NULL when set_boundary_detj
+ * follows); q1d <= 0 selects p + 1, and p + 1 and p + 2 are supported (else ECM2_ERR_UNSUPPORTED).
+ * A distributed local form refuses it (ECM2_ERR_UNSUPPORTED).  set_boundary_detj: FaceGeometricFactors::
+ * detJ, device [nbe][q1d^2], valid until assemble.  add_boundary_integrator: integrator ECM2_MASS only
+ * (ECM2_DIFFUSION: ECM2_ERR_UNSUPPORTED); coeff_kind ECM2_COEFF_CONSTANT (data[0], host) or _QUAD
+ * (device [nbe][q1d^2], boundary element order), other kinds ECM2_ERR_ARG; marker host [n_marker],
+ * 0 / 1 per boundary attribute, NULL: every face.  The markers are folded into the face data at
+ * assemble; only faces some integrator acts on are kept.  Mult (every kernel mode), AddMult,
+ * MultTranspose, the operator wrapper, PCG and the ODE steps then include the term: one face apply
+ * and a fixed-order add pass (no atomics) after the volume result; AssembleDiagonal adds the face
+ * diagonal with the reference's shared-vector marker rule (:441-452).  ecm2_pa_form_energy_parts is 0
+ * for such a form (the folded energy would miss the face term). */
+int ecm2_pa_form_set_boundary(ecm2_pa_form *f, int nbe, const int *bdr_map, const int *bdr_attr,
+                              const double *bdr_nodes, int q1d);
+int ecm2_pa_form_set_boundary_detj(ecm2_pa_form *f, const double *detj);
+int ecm2_pa_form_add_boundary_integrator(ecm2_pa_form *f, int integrator, int coeff_kind, const double *data,
+                                         const int *marker, int n_marker);
+/* pa_data of boundary integrator `index` (in the order added) in the reference's layout, host
+ * out[nbe][q1d^2]; zeros on the faces its marker excludes.  After assemble. */
+int ecm2_pa_form_get_boundary_qdata(ecm2_pa_form *f, int index, double *out, void *stream);
+/* Introspection (any output may be NULL): boundary elements, boundary integrators, faces kept by
+ * the last assemble, points per direction of the face rule. */
+int ecm2_pa_form_boundary_info(const ecm2_pa_form *f, int *nbe, int *n_integrators, int *n_active, int *q1d);
 int ecm2_pa_form_set_kernel(ecm2_pa_form *f, int kernel);
 /* Scatter of the fused thread-per-element kernel (no reference counterpart: the
  * reference's ElementRestriction::MultTranspose, restriction.cpp:146-186, is the
@@ -412,6 +466,21 @@ int ecm2_linear_form_add_domain_integrator(ecm2_linear_form *lf, int coeff_kind,
  * the integrators in the order they were added (the first's R^T stores, the later ones add,
  * :64-67).  No atomics: two calls on the same inputs give bitwise equal vectors. */
 int ecm2_linear_form_assemble(ecm2_linear_form *lf, double *b /* device [ndofs], overwritten */, void *stream);
+/* LinearForm::AddBoundaryIntegrator(new BoundaryLFIntegrator(g)[, bdr_marker]): the boundary loop of
+ * LinearFormExtension::Assemble (fem/linearform_ext.cpp:70-111: markers[e] = attr[e] > 0 &&
+ * marker[attr[e] - 1], each integrator's face vectors transposed and added into b after the domain
+ * integrators) and BoundaryLFIntegrator::AssembleDevice + BLFEvalAssemble3D
+ * (fem/integ/lininteg_boundary.cpp:74-153, 214-228).  set_boundary: as ecm2_pa_form_set_boundary;
+ * q1d <= 0 selects the integrator's default rule of order a p + b, a = b = 1 (lininteg.hpp:200):
+ * (p + 1) / 2 + 1 points per direction; that, p + 1 and p + 2 are supported.  set_boundary_detj:
+ * FaceGeometricFactors::detJ (mesh/mesh.cpp:15275-15334), device [nbe][q1d^2], read at every assemble.
+ * coeff_kind: ECM2_COEFF_CONSTANT (data[0], host) or _QUAD (device [nbe][q1d^2], boundary element
+ * order), anything else ECM2_ERR_ARG.  A form with boundary integrators only still overwrites b. */
+int ecm2_linear_form_set_boundary(ecm2_linear_form *lf, int nbe, const int *bdr_map, const int *bdr_attr,
+                                  const double *bdr_nodes, int q1d);
+int ecm2_linear_form_set_boundary_detj(ecm2_linear_form *lf, const double *detj);
+int ecm2_linear_form_add_boundary_integrator(ecm2_linear_form *lf, int coeff_kind, const double *data,
+                                             const int *marker, int n_marker);
 /* Introspection (any output may be NULL). */
 int ecm2_linear_form_info(const ecm2_linear_form *lf, int *ne, int *ndofs, int *d1d, int *q1d, int *n_integrators);
 /* ~LinearForm. */
