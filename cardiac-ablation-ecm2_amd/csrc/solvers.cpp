@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <memory>
 
 namespace ecm2
@@ -136,6 +137,9 @@ PCGWork &pcg_work()
 PCGResult pcg_solve(LinOp &A, const int *ess, int n_ess, const double *b, double *x, double rel_tol,
                     double abs_tol, int max_iter, bool jacobi, hipStream_t s)
 {
+   // k_pcg_update_xd / k_pcg_step_r / k_pcg_finish_x read and write the caller's x two entries at a
+   // time; refused here, before anything is enqueued (the work vectors are allocations of their own)
+   ECM2_VERIFY(((uintptr_t)x % 16) == 0, ERR_ARG, "PCG: x must be 16-byte aligned (got " << (const void *)x << ")");
    const int n = A.size();
    PCGResult res;
    PCGWork &w = pcg_work();

@@ -360,7 +360,9 @@ void ecm2_pa_form_destroy(ecm2_pa_form *f);
 /* CGSolver::Mult solvers.cpp:869-1004)                                       */
 /* ------------------------------------------------------------------------ */
 /* ess: device int [n_ess] essential dofs (DIAG_ONE).  b, x device [ndofs];
- * x is overwritten (iterative_mode = false).  jacobi != 0 -> OperatorJacobiSmoother.
+ * x is overwritten (iterative_mode = false) and must be 16-byte aligned (the update kernels move two
+ * entries per access; a view at an odd element offset returns ECM2_ERR_ARG before anything is
+ * enqueued).  jacobi != 0 -> OperatorJacobiSmoother.
  * iterations = CGSolver's final_iter, final_norm = sqrt((B r, r)) (the raw (B r, r) when it is
  * negative).  CGSolver's stops: converged, max_iter, (B r, r) < 0 or (A d, d) == 0 (not
  * converged: ecm2_pcg_last_converged() == 0); a non-finite (B r, r) or (A d, d), where the
@@ -397,7 +399,8 @@ int ecm2_operator_mult(ecm2_operator *op, const double *x, double *y, void *stre
 /* ConstrainedOperator (operator.cpp:586-646) + CGSolver::Mult (solvers.cpp:869-1004) +
  * OperatorJacobiSmoother on any operator; with the RCCL form every rank calls it
  * collectively (dots are summed with ncclAllReduce, as the reference's parallel
- * InnerProduct sums with MPI_Allreduce). */
+ * InnerProduct sums with MPI_Allreduce).  x must be 16-byte aligned, as for ecm2_pcg_solve
+ * (ECM2_ERR_ARG otherwise, before anything is enqueued). */
 int ecm2_operator_pcg(ecm2_operator *op, const int *ess, int n_ess, const double *b, double *x,
                       double rel_tol, double abs_tol, int max_iter, int jacobi, int *iterations,
                       double *final_norm, void *stream);
