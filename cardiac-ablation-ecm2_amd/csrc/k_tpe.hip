@@ -167,6 +167,167 @@ __device__ __forceinline__ void tpe_assemble_store(double (&Yo)[D * D * D], cons
          }
 }
 
+// Lane l's copy of lane l + N's value within its 16-lane DPP row (N = 1, 4: the x and y neighbours
+// of lane = ex + 4 ey + 16 ez), two 32-bit row shifts and no LDS.  A lane whose source lies outside
+// the row keeps its own value; the lattice path never selects it (tpe_lane_flags_in_row).
+template <int N>
+__device__ __forceinline__ double dpp_row_down(double v)
+{
+   static_assert(N >= 1 && N <= 15, "row_shl");
+   int lo = __double2loint(v), hi = __double2hiint(v);
+   lo = __builtin_amdgcn_update_dpp(lo, lo, 0x100 + N, 0xf, 0xf, false);
+   hi = __builtin_amdgcn_update_dpp(hi, hi, 0x100 + N, 0xf, 0xf, false);
+   return __hiloint2double(hi, lo);
+}
+
+// tpe_assemble_store for the blocks of a lattice form that writes partial slots (regular blocks RM 1,
+// lattice-map blocks RM 3; p = 2): the same additions in the same order, without a branch or an LDS
+// round trip per value.
+// * x and y merges: DPP row shifts by 1 and 4.  The planner grants the lattice classes only to blocks
+//   whose x / y receive bits sit on lanes with ex < 3 / ey < 3 (tpe_lane_flags_in_row), so a
+//   receiving lane's source is in its row.  z merge (16 lanes): all 18 permutes, then one wait.
+//   Its source lane (l + 16) & 63 wraps for lanes 48-63, which never receive (the same predicate).
+//   Receive and clear are selects on the result; a sum is selected, never a 0.0 added (-0.0 stays).
+// * across waves: the sends, the three barriers and the order of the adds as in the generic function;
+//   a receiving lane issues its 9 LDS reads together.
+// * store: the outputs grouped by the low faces they lie on (8 groups), one "not sent" predicate per
+//   group and one store per value; the destination (y + d or the face-grouped partial slot) by
+//   select.  With dx, dy, dz compile-time an output meets at most one face test per axis, for the
+//   shared flag (regular blocks) and for the slot (tpe_surface_index's order: z, then y, then x).
+//   Regular blocks: d = the lane's corner dof + the wave-uniform dx sx + dy sy + dz sz.
+template <int RM, int XR, bool SPLIT>
+__device__ __forceinline__ void tpe_assemble_store_lattice(double (&Yo)[27], int fl, int blk, int lane, bool active,
+                                                           int n_owned, double *__restrict__ y, double *__restrict__ yg,
+                                                           double *__restrict__ part, double *xb, int w, TpeReg rg,
+                                                           int pstride, const int *__restrict__ lm)
+{
+   static_assert(RM == 1 || RM == 3, "lattice blocks");
+   constexpr int D = 3, ND = 27;
+   static_assert(XR >= XwaveRows<D>::R, "staging rows");
+   // (an opaque lane: what the epilogue derives from it is computed here, not kept across the plane loop)
+   asm volatile("" : "+v"(lane));
+   const int ex = lane & 3, ey = (lane >> 2) & 3, ez = lane >> 4;
+   // lattice-map blocks: the store's map entries, loaded before the merges (as tpe_assemble_store)
+   int lo = 0;
+   asm volatile("" : "+v"(lo));
+   int gs[ND];
+#pragma unroll
+   for (int a = 0; a < ND; a++)
+   {
+      gs[a] = 0;
+      if (RM == 3 && active) { gs[a] = lm[tpe_lattice_slot(D, 2 * ex + a % D, 2 * ey + (a / D) % D, 2 * ez + a / (D * D)) + lo]; }
+   }
+   auto send = [&](int dir, int e_dir, int sent_bit, auto face) {
+      if (e_dir == 0 && (fl & sent_bit))
+      {
+#pragma unroll
+         for (int k = 0; k < D * D; k++) { xb[((w * XR) + dir * D * D + k) * 64 + lane] = Yo[face(0, k % D, k / D)]; }
+      }
+   };
+   auto settle = [&](double (&v)[D * D], int recv_bit, int sent_bit, auto face) {
+      const bool recv = fl & recv_bit, sent = fl & sent_bit;
+#pragma unroll
+      for (int k = 0; k < D * D; k++)
+      {
+         const int ar = face(D - 1, k % D, k / D), as = face(0, k % D, k / D);
+         const double sum = Yo[ar] + v[k];
+         Yo[ar] = recv ? sum : Yo[ar];
+         Yo[as] = sent ? 0.0 : Yo[as];
+      }
+   };
+   auto exchange = [&](int dir, int delta, auto face) {
+      __syncthreads();
+      if (fl & (64 << dir))
+      {
+         const int pw = (fl >> (9 + 3 * dir)) & 7;
+         double v[D * D];
+#pragma unroll
+         for (int k = 0; k < D * D; k++) { v[k] = xb[((pw * XR) + dir * D * D + k) * 64 + lane - 3 * delta]; }
+#pragma unroll
+         for (int k = 0; k < D * D; k++) { Yo[face(D - 1, k % D, k / D)] += v[k]; }
+      }
+   };
+   auto fx = [](int s, int i, int j) { return (j * D + i) * D + s; };  // x: (dz=j, dy=i)
+   auto fy = [](int s, int i, int j) { return (j * D + s) * D + i; };  // y: (dz=j, dx=i)
+   auto fz = [](int s, int i, int j) { return (s * D + j) * D + i; };  // z: (dy=j, dx=i)
+   double v[D * D];
+   send(0, ex, 2, fx);
+#pragma unroll
+   for (int k = 0; k < D * D; k++) { v[k] = dpp_row_down<1>(Yo[fx(0, k % D, k / D)]); }
+   settle(v, 1, 2, fx);
+   exchange(0, 1, fx);
+   send(1, ey, 8, fy);
+#pragma unroll
+   for (int k = 0; k < D * D; k++) { v[k] = dpp_row_down<4>(Yo[fy(0, k % D, k / D)]); }
+   settle(v, 4, 8, fy);
+   exchange(1, 4, fy);
+   send(2, ez, 32, fz);
+   const int src16 = ((lane + 16) & 63) * 4;
+#pragma unroll
+   for (int k = 0; k < D * D; k++)
+   {
+      const double s = Yo[fz(0, k % D, k / D)];
+      const int l32 = __builtin_amdgcn_ds_bpermute(src16, __double2loint(s)), h32 = __builtin_amdgcn_ds_bpermute(src16, __double2hiint(s));
+      v[k] = __hiloint2double(h32, l32);
+   }
+   settle(v, 16, 32, fz);
+   exchange(2, 16, fz);
+   if (!active) { return; }
+   const bool sx = fl & 2, sy = fl & 8, sz = fl & 32;
+   // this lane on the block's low / high face per axis (regular blocks: and that face shared)
+   const bool x0 = ex == 0, x1 = ex == 3, y0 = ey == 0, y1 = ey == 3, z0 = ez == 0, z1 = ez == 3;
+   const bool hx0 = x0 && (rg.mask & 1), hx1 = x1 && (rg.mask & 2), hy0 = y0 && (rg.mask & 4), hy1 = y1 && (rg.mask & 8),
+              hz0 = z0 && (rg.mask & 16), hz1 = z1 && (rg.mask & 32);
+   constexpr int L = 9;
+   // tpe_surface_index per face group, at the lane's corner (X, Y, Z) = 2 (ex, ey, ez)
+   const int sZ = 2 * ey * L + 2 * ex;                                // Z = 0 (+ L L: Z = L - 1)
+   const int sY = 2 * L * L + (2 * ez - 1) * L + 2 * ex;              // Y = 0 (+ (L - 2) L: Y = L - 1)
+   const int sX = 2 * L * L + 2 * (L - 2) * L + (2 * ez - 1) * (L - 2) + 2 * ey - 1;  // X = 0 (+ (L - 2)^2: X = L - 1)
+   const int d0 = rg.base + 2 * ex * rg.sx + 2 * ey * rg.sy + 2 * ez * rg.sz;
+   double *const pb = part + (size_t)blk * pstride;
+   auto store = [&](const int dx, const int dy, const int dz) {
+      const int a = (dz * D + dy) * D + dx;
+      int d, si = 0;
+      bool shared;
+      if (RM == 1)
+      {
+         d = d0 + (dx * rg.sx + dy * rg.sy + dz * rg.sz);
+         shared = (dx == 0 && hx0) || (dx == D - 1 && hx1) || (dy == 0 && hy0) || (dy == D - 1 && hy1) ||
+                  (dz == 0 && hz0) || (dz == D - 1 && hz1);
+      }
+      else
+      {
+         d = bdof(gs[a]);
+         shared = bshared(gs[a]);
+      }
+      if (dx == 0) { si = x0 ? sX + dz * (L - 2) + dy : si; }
+      if (dx == D - 1) { si = x1 ? sX + (L - 2) * (L - 2) + dz * (L - 2) + dy : si; }
+      if (dy == 0) { si = y0 ? sY + dz * L + dx : si; }
+      if (dy == D - 1) { si = y1 ? sY + (L - 2) * L + dz * L + dx : si; }
+      if (dz == 0) { si = z0 ? sZ + dy * L + dx : si; }
+      if (dz == D - 1) { si = z1 ? sZ + L * L + dy * L + dx : si; }
+      double *own = y + d;
+      if (RM != 1 && SPLIT) { own = d < n_owned ? own : yg + (d - n_owned); }  // (regular blocks: every dof owned)
+      double *dst = shared ? pb + si : own;
+      *dst = Yo[a];
+   };
+#pragma unroll
+   for (int g = 0; g < 8; g++)
+   {
+      const bool lx = g & 1, ly = g & 2, lz = g & 4;  // the group's outputs lie on these low faces
+      if ((lx && sx) || (ly && sy) || (lz && sz)) { continue; }
+#pragma unroll
+      for (int dz = 0; dz < D; dz++)
+#pragma unroll
+         for (int dy = 0; dy < D; dy++)
+#pragma unroll
+            for (int dx = 0; dx < D; dx++)
+            {
+               if ((dx == 0) == lx && (dy == 0) == ly && (dz == 0) == lz) { store(dx, dy, dz); }
+            }
+   }
+}
+
 // Full per-point qdata (BLOCKED layout), per quadrature row (qy, qz): the 27 gathered dofs
 // live in LDS (a private [a][lane] slot per wave: conflict-free ds_read_b64), which frees the
 // VGPRs to hold the NEXT row's qdata in flight while the current row is computed (double
@@ -759,7 +920,8 @@ constexpr bool ts_gather_is_permutation()
 }
 static_assert(ts_gather_is_permutation(), "the gather order permutes the slots within each 64-slot step");
 __constant__ LatticeTsGather kLatTsGather3 = LatticeTsGather();
-// The padded LDS slot (tsl_slot, kernels.hpp) of each lattice slot j (regular blocks: slot order).
+// The padded LDS slot (tsl_slot, kernels.hpp) of each lattice slot j (regular blocks: slot order): the TIGHT
+// instantiations of k_apply_tpe_ts, which keep the two 16-bit tables.
 struct LatticeTsl
 {
    static constexpr int N = tpe_lattice_points(3);
@@ -772,6 +934,24 @@ struct LatticeTsl
    }
 };
 __constant__ LatticeTsl kLatTsl3 = LatticeTsl();
+// Regular blocks gather in slot order: entry j holds the lattice coordinates of slot j (as kLatXYZ3: X |
+// Y << 5 | Z << 10) | its padded LDS slot (tsl_slot, kernels.hpp) << 16 -- one 32-bit load per step.
+struct LatticeTsReg
+{
+   static constexpr int N = tpe_lattice_points(3);
+   unsigned v[N];
+   constexpr LatticeTsReg() : v()
+   {
+      for (int Z = 0; Z < 9; Z++)
+         for (int Y = 0; Y < 9; Y++)
+            for (int X = 0; X < 9; X++)
+            {
+               v[tpe_lattice_slot(3, X, Y, Z)] = (unsigned)(X | Y << 5 | Z << 10) | (unsigned)tsl_slot(X, Y, Z) << 16;
+            }
+   }
+};
+static_assert(tsl_points() < (1 << 16), "the padded slot fits the entry's high half");
+__constant__ LatticeTsReg kLatTsReg3 = LatticeTsReg();
 
 // pairs of the TRILINEAR coefficients (c[3 (k - 1) + i] two per pair) that only the per-plane J
 // pieces read: k = 0, 1, 3 -> f = 0..5, 9..11 -> pairs 0, 1, 2, 5 (pair 4 also holds f = 8, a row one)
@@ -1085,7 +1265,9 @@ k_apply_tpe_tlb(int ne, int blk_begin, int blk_end, int n_owned, const int *__re
 // per-point stream at all.  x and T' are gathered once per lattice point (the block's 729 lattice
 // slots, as k_apply_tpe_tlb) into one LDS region that the cross-wave face exchange reuses afterwards.
 // Lattice blocks only (RM 1 regular, 3 lattice-map), p = 2.
-template <int D, int Q, bool SPLIT, int RM, int MM, bool LAW, bool CD>
+// PART: the launch writes partial slots (part != null): the lattice epilogue
+// (tpe_assemble_store_lattice); scatter = atomic keeps the generic one, and so do the TIGHT instantiations.
+template <int D, int Q, bool SPLIT, int RM, int MM, bool LAW, bool CD, bool PART>
 __global__ void __launch_bounds__(256, 2)
 k_apply_tpe_ts(int ne, int blk_begin, int blk_end, int n_owned, const int *__restrict__ gmap,
                const double *__restrict__ qdd, const double *__restrict__ qdm,
@@ -1132,54 +1314,131 @@ k_apply_tpe_ts(int ne, int blk_begin, int blk_end, int n_owned, const int *__res
       for (int qx = 0; qx < Q; qx++) { aq[qx] = MM == 1 ? __builtin_nontemporal_load(qa + (size_t)(row * Q + qx) * 64) : 0.0; }
    };
    double mel = 0.0;  // MM 2: the element's (c alpha) det J, [blk][lane]
-   if (wave_on)
+   // TIGHT: the instantiations at 256 VGPRs (a per-point mass, the laws at the point and the general flux
+   // together) keep the previous prologue and the generic epilogue: with the gather-first prologue or
+   // the lattice epilogue they spill a value across the plane loop.
+   constexpr bool TIGHT = LAW && MM == 1 && !CD;
+   if constexpr (TIGHT)
    {
-      const double *qc = qdd + (size_t)blk * 3 * 128 + lane * 2;
-#pragma unroll
-      for (int k = 0; k < 3; k++) { ce[k] = ld2(qc + k * 128); }
-      load_row(0, ra[0]);
-      load_row(1, ra[1]);
-      if (MM == 2) { mel = qdm[(size_t)blk * 64 + lane]; }
-      if (RM == 1)
+      if (wave_on)
       {
-         const int *r = treg + (size_t)blk * 8;  // wave-uniform: scalar loads
-         rg = TpeReg{r[0], r[1], r[2], r[3], r[4]};
-      }
-      const int *lm = lmap + (size_t)blk * NLP;
-#pragma unroll
-      for (int k = 0; k < (NLP + 63) / 64; k++)
-      {
-         const int p = lane + 64 * k;
-         if (p < NLP)
+         const double *qc = qdd + (size_t)blk * 3 * 128 + lane * 2;
+   #pragma unroll
+         for (int k = 0; k < 3; k++) { ce[k] = ld2(qc + k * 128); }
+         load_row(0, ra[0]);
+         load_row(1, ra[1]);
+         if (MM == 2) { mel = qdm[(size_t)blk * 64 + lane]; }
+         if (RM == 1)
          {
-            // lattice-map blocks: the slots dealt for the writes' banks (the lanes of a step still read the
-            // same map and snapshot lines); regular blocks: slot order (j = p), whose x / T' gathers of a
-            // step stay on few lines -- dealt, they cost the structured Mult 3% (profiles/r6/ab_gather.txt)
-            int j, ls;
-            if (RM == 3)
+            const int *r = treg + (size_t)blk * 8;  // wave-uniform: scalar loads
+            rg = TpeReg{r[0], r[1], r[2], r[3], r[4]};
+         }
+         const int *lm = lmap + (size_t)blk * NLP;
+   #pragma unroll
+         for (int k = 0; k < (NLP + 63) / 64; k++)
+         {
+            const int p = lane + 64 * k;
+            if (p < NLP)
             {
-               const unsigned g = kLatTsGather3.v[p];
-               j = (int)(g & 0xffff);
-               ls = (int)(g >> 16);
+               // lattice-map blocks: the slots dealt for the writes' banks (the lanes of a step still read the
+               // same map and snapshot lines); regular blocks: slot order (j = p), whose x / T' gathers of a
+               // step stay on few lines -- dealt, they cost the structured Mult 3% (profiles/r6/ab_gather.txt)
+               int j, ls;
+               if (RM == 3)
+               {
+                  const unsigned g = kLatTsGather3.v[p];
+                  j = (int)(g & 0xffff);
+                  ls = (int)(g >> 16);
+               }
+               else
+               {
+                  j = p;
+                  ls = kLatTsl3.v[p];
+               }
+               int d;
+               if (RM == 3) { d = bdof(lm[j]); }
+               else
+               {
+                  const unsigned v = lattice_xyz<D>(j);
+                  d = rg.base + (int)(v & 31) * rg.sx + (int)((v >> 5) & 31) * rg.sy + (int)(v >> 10) * rg.sz;
+               }
+               // (lattice-map blocks: the snapshot is stored in their slot order, a contiguous read)
+               sPL[ls] = v2d{(!SPLIT || d < n_owned) ? x[d] : xg[d - n_owned], RM == 3 ? tsn[(size_t)blk * NLP + j] : tsn[d]};
             }
-            else
-            {
-               j = p;
-               ls = kLatTsl3.v[p];
-            }
-            int d;
-            if (RM == 3) { d = bdof(lm[j]); }
-            else
-            {
-               const unsigned v = lattice_xyz<D>(j);
-               d = rg.base + (int)(v & 31) * rg.sx + (int)((v >> 5) & 31) * rg.sy + (int)(v >> 10) * rg.sz;
-            }
-            // (lattice-map blocks: the snapshot is stored in their slot order, a contiguous read)
-            sPL[ls] = v2d{(!SPLIT || d < n_owned) ? x[d] : xg[d - n_owned], RM == 3 ? tsn[(size_t)blk * NLP + j] : tsn[d]};
          }
       }
+      __syncthreads();  // the lattices are read by every lane of the wave
    }
-   __syncthreads();  // the lattices are read by every lane of the wave
+   else
+   {
+      // The gather, ahead of everything else the prologue loads: the plane loop cannot start before the
+      // lattice image is in LDS, so the x / T' loads go out first -- their table entries (one 32-bit entry per
+      // step) before the block's scalars, then the loads themselves -- and the coefficient and row loads,
+      // which the first row needs only at its points, follow them; loads return in order, so the image's
+      // writes wait for the gather alone.  (With the C and row loads first, the gather's addresses waited
+      // for them: one more HBM round trip before the first plane.)  Lattice-map blocks: the slots dealt for
+      // the writes' banks (the lanes of a step still read the same map and snapshot lines); regular blocks:
+      // slot order, whose x / T' gathers of a step stay on few lines -- dealt, they cost the structured Mult
+      // 3% (profiles/r6/ab_gather.txt).
+      constexpr int NGS = (NLP + 63) / 64;
+      unsigned gt[NGS];
+   #pragma unroll
+      for (int k = 0; k < NGS; k++)
+      {
+         const int p = lane + 64 * k;
+         gt[k] = p < NLP ? (RM == 3 ? kLatTsGather3.v[p] : kLatTsReg3.v[p]) : 0u;
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (wave_on)
+      {
+         if (RM == 1)
+         {
+            const int *r = treg + (size_t)blk * 8;  // wave-uniform: scalar loads
+            rg = TpeReg{r[0], r[1], r[2], r[3], r[4]};
+         }
+         const int *lm = lmap + (size_t)blk * NLP;
+         v2d gv[NGS], *gp[NGS];  // (the image addresses too: nothing of the writes is left to compute behind the later loads)
+   #pragma unroll
+         for (int k = 0; k < NGS; k++)
+         {
+            const int p = lane + 64 * k;
+            gv[k] = v2d{0.0, 0.0};
+            gp[k] = sPL + (gt[k] >> 16);
+            if (p < NLP)
+            {
+               const unsigned g = gt[k];
+               const int j = RM == 3 ? (int)(g & 0xffff) : p;
+               int d;
+               if (RM == 3) { d = bdof(lm[j]); }
+               else { d = rg.base + (int)(g & 31) * rg.sx + (int)((g >> 5) & 31) * rg.sy + (int)((g >> 10) & 31) * rg.sz; }
+               // (lattice-map blocks: the snapshot is stored in their slot order, a contiguous read)
+               gv[k] = v2d{(!SPLIT || d < n_owned) ? x[d] : xg[d - n_owned], RM == 3 ? tsn[(size_t)blk * NLP + j] : tsn[d]};
+            }
+         }
+         __builtin_amdgcn_sched_barrier(0);
+         const double *qc = qdd + (size_t)blk * 3 * 128 + lane * 2;
+   #pragma unroll
+         for (int k = 0; k < 3; k++) { ce[k] = ld2(qc + k * 128); }
+         load_row(0, ra[0]);
+         load_row(1, ra[1]);
+         if (MM == 2) { mel = qdm[(size_t)blk * 64 + lane]; }
+         __builtin_amdgcn_sched_barrier(0);
+   #pragma unroll
+         for (int k = 0; k < NGS; k++)
+         {
+            if (lane + 64 * k < NLP) { *gp[k] = gv[k]; }
+         }
+      }
+      // The lattices are read by every lane of the wave, and by this wave alone (sPL = sU[w]): the energy
+      // fold reads its own image, the face exchange reads other waves' regions behind its own barriers and
+      // each wave parks its sends in its own region.  So no workgroup barrier: LDS serves a wave's
+      // instructions in order; the wait and the wave-scope fences keep the compiler from moving a read
+      // above the gather's writes.
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+   }
    if (wave_on)
    {
       auto lane_base = [&](int cx, int cy) {  // (the padded image: tsl_slot)
@@ -1352,9 +1611,17 @@ k_apply_tpe_ts(int ne, int blk_begin, int blk_end, int n_owned, const int *__res
       __syncthreads();
       if (threadIdx.x == 0) { en[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]); }
    }
-   tpe_assemble_store<D, SPLIT, false, true, true, XRS>(Yo, mp, wave_on ? lane_flags[(size_t)blk * 64 + lane] : 0, blk, lane,
-                                                       active, n_owned, y, yg, part, &sU[0][0][0], w, wave_on, rg, regf,
-                                                       pstride, lmap ? lmap + (size_t)blk * NLP : nullptr);
+   const int fl = wave_on ? lane_flags[(size_t)blk * 64 + lane] : 0;
+   if constexpr (PART && !TIGHT)
+   {
+      tpe_assemble_store_lattice<RM, XRS, SPLIT>(Yo, fl, blk, lane, active, n_owned, y, yg, part, &sU[0][0][0], w, rg, pstride,
+                                                 RM == 3 && wave_on ? lmap + (size_t)blk * NLP : nullptr);
+   }
+   else
+   {
+      tpe_assemble_store<D, SPLIT, false, true, true, XRS>(Yo, mp, fl, blk, lane, active, n_owned, y, yg, part, &sU[0][0][0], w,
+                                                          wave_on, rg, regf, pstride, lmap ? lmap + (size_t)blk * NLP : nullptr);
+   }
 }
 
 // Latency variant of k_apply_tpe_sf for small block ranges (the boundary elements of the
@@ -1678,10 +1945,15 @@ void launch_tpe(const ApplyArgs &a, const TpeArgs &t, const Basis1D &b, const do
          ECM2_VERIFY(t.tmass == (MASS ? t.tmass : 0) && (t.tmass != 0) == MASS && a.pw == (t.tmass == 1 ? 1 : 0) &&
                         t.treg && (t.treg_all || t.tlat_all) && t.tsnap_kind == (t.treg_all ? 1 : 2),
                      ERR_INTERNAL, "coefficient snapshot needs lattice blocks and matching mass values");
+#define ECM2_TS_P(RM, MM, LAW, CD, PART)                                                                            \
+   if ((a.part != nullptr) == PART)                                                                                 \
+   {                                                                                                                \
+      hipLaunchKernelGGL((k_apply_tpe_ts<3, 4, SPLIT, RM, MM, LAW, CD, PART>), grid, block, 0, s, a.ne, a.blk_begin, \
+                         a.blk_end, a.n_owned, a.gmap, a.qdd, a.qdm, a.x, a.xg, t.tsnap, a.y, a.yg, b, t.bw,         \
+                         t.lane_flags, a.part, t.treg, t.part_stride, t.lmap, t.qw, t.law_d, t.law_m, a.en);         \
+   }
 #define ECM2_TS(RM, MM, LAW, CD)                                                                                    \
-   hipLaunchKernelGGL((k_apply_tpe_ts<3, 4, SPLIT, RM, MM, LAW, CD>), grid, block, 0, s, a.ne, a.blk_begin, a.blk_end, \
-                      a.n_owned, a.gmap, a.qdd, a.qdm, a.x, a.xg, t.tsnap, a.y, a.yg, b, t.bw, t.lane_flags, a.part,   \
-                      t.treg, t.part_stride, t.lmap, t.qw, t.law_d, t.law_m, a.en)
+   ECM2_TS_P(RM, MM, LAW, CD, true) else ECM2_TS_P(RM, MM, LAW, CD, false)
 #define ECM2_TS_MM(RM, LAW, CD)                                                                                     \
    if (!MASS) { ECM2_TS(RM, 0, LAW, CD); }                                                                          \
    else if (t.tmass == 1) { ECM2_TS(RM, 1, LAW, CD); }                                                              \
@@ -1700,6 +1972,7 @@ void launch_tpe(const ApplyArgs &a, const TpeArgs &t, const Basis1D &b, const do
 #undef ECM2_TS_LAW
 #undef ECM2_TS_MM
 #undef ECM2_TS
+#undef ECM2_TS_P
       }
       else { ECM2_VERIFY(false, ERR_INTERNAL, "coefficient snapshot: p = 2 forms with the diffusion integrator"); }
       return;

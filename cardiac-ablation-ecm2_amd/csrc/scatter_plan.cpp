@@ -668,6 +668,16 @@ bool block_lattice_slots(const BlockView &V, int b, std::vector<int> &lm)
 }
 } // namespace
 
+// (brick blocks satisfy it by construction: lanes 3 and 4, or 12 and 16, are not x or y neighbours)
+bool tpe_lane_flags_in_row(const int *flags64)
+{
+   for (int l = 0; l < 64; l++)
+   {
+      if (((flags64[l] & 1) && (l & 3) == 3) || ((flags64[l] & 4) && ((l >> 2) & 3) == 3) || ((flags64[l] & 16) && l >= 48)) { return false; }
+   }
+   return true;
+}
+
 TpePlan build_tpe_plan(int ne, int D, int ndofs, int n_owned, const std::vector<int> &gmap_host,
                        const std::vector<int> &perm_host, const std::vector<int> &splits, int latency_from,
                        bool lattice_layout, const PlanOptions &opt)
@@ -700,8 +710,9 @@ TpePlan build_tpe_plan(int ne, int D, int ndofs, int n_owned, const std::vector<
       }
    }
    // Decided per block (a partitioned rank's interior blocks are regular, its boundary blocks are
-   // not); treg_all / tlat_all when every block is.  Incomplete blocks and blocks the latency
-   // kernel applies store [a][lane] slots: neither regular nor lattice-slot.
+   // not); treg_all / tlat_all when every block is.  Incomplete blocks, blocks the latency kernel
+   // applies and blocks with an in-wave x / y link outside a 16-lane row (tpe_lane_flags_in_row)
+   // store [a][lane] slots: neither regular nor lattice-slot.
    const BlockView V{D, ND, n_owned, P.gmap_blk, holds, hcount};
    const int ns = tpe_surface_points(D), NL = tpe_lattice_points(D);
    std::vector<char> unit(nblk, 0);  // 1 regular, 2 lattice slots
@@ -711,6 +722,10 @@ TpePlan build_tpe_plan(int ne, int D, int ndofs, int n_owned, const std::vector<
       for (int b = 0; b < nblk; b++)
       {
          if ((long)(b + 1) * 64 > ne || (latency_from >= 0 && b >= latency_from)) { continue; }
+         // The snapshot kernel's lattice epilogue moves the x and y faces by DPP row shifts.  (The block
+         // classes are shared: the other lattice kernels -- k_apply_tpe_tlb, k_apply_tpe_sf, the diagonal --
+         // shuffle through LDS and do not need the condition, but lose the class with it.  No brick fails it.)
+         if (!tpe_lane_flags_in_row(&P.lane_flags[(size_t)b * 64])) { continue; }
          if (block_regular(V, b, &reg[(size_t)b * 8])) { unit[b] = 1; }
          else if (block_lattice_slots(V, b, lm))
          {

@@ -64,6 +64,12 @@ struct TpePlan : TpePlanInfo
    std::vector<int> lmap;       // [blk][tpe_lattice_points] lattice maps; empty: no lattice-slot block
    SharedPlan shared;
 };
+// What the lattice blocks' epilogue (tpe_assemble_store_lattice, k_tpe.hip) needs of a block's 64 merge
+// flags (lane = ex + 4 ey + 16 ez): an in-wave x receive bit (1) only on lanes with ex < 3 and a y
+// receive bit (4) only on lanes with ey < 3, so the sending lane l + 1 / l + 4 lies in the receiver's
+// 16-lane DPP row; and a z receive bit (16) only on lanes below 48, so lane l + 16 exists.  build_tpe_plan
+// classes a block that fails it neither regular nor lattice-slot, for every kernel that reads the classes.
+bool tpe_lane_flags_in_row(const int *flags64);
 // perm_host empty: derive the order.  lattice_layout: the AFFINE / TRILINEAR qdata layouts (cross-wave
 // links, regular and lattice-slot blocks).
 TpePlan build_tpe_plan(int ne, int D, int ndofs, int n_owned, const std::vector<int> &gmap_host,
