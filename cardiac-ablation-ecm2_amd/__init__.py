@@ -31,6 +31,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libecm2pa.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ecm2_pa.h")
 
 MASS, DIFFUSION = 0, 1
+CONVECTION = 2  # ConvectionIntegrator (the serial BilinearForm only)
 COEFF_CONSTANT, COEFF_QUAD, COEFF_GRIDFUNC_AFFINE, COEFF_GRIDFUNC_PERFUSION = 0, 1, 2, 3
 COEFF_QUAD_VECTOR, COEFF_QUAD_SYMMATRIX, COEFF_QUAD_MATRIX = 4, 5, 6
 COEFF_CONST_VECTOR, COEFF_CONST_SYMMATRIX, COEFF_CONST_MATRIX = 7, 8, 9
@@ -132,6 +133,8 @@ def load_library(path: str = LIB_PATH):
         "ecm2_pa_form_restriction_mult": (i32, [vp, vp, vp, vp]),
         "ecm2_pa_form_restriction_mult_transpose": (i32, [vp, vp, vp, vp]),
         "ecm2_pa_form_integrator_add_mult": (i32, [vp, i32, vp, vp, vp]),
+        "ecm2_pa_form_integrator_add_mult_transpose": (i32, [vp, i32, vp, vp, vp]),
+        "ecm2_pa_form_convection_info": (i32, [vp, ip, ip, ip]),
         "ecm2_pa_form_get_qdata": (i32, [vp, i32, vp, vp]),
         "ecm2_pa_form_info": (i32, [vp, ip, ip, ip, ip, ip, ip]),
         "ecm2_pa_form_timing": (i32, [vp, i32]),
@@ -579,6 +582,17 @@ class DiffusionIntegrator:
         self.coeff = coeff if coeff is not None else ConstantCoefficient(1.0)
 
 
+class ConvectionIntegrator:
+    """ConvectionIntegrator(vel, alpha): alpha (vel . grad u, v) -- the blood-flow advection of the bioheat
+    operator.  coeff: a VectorCoefficient (a 3-vector, or CUDA float64 [ne][nq][3] at the form's quadrature
+    points); the qdata is built from it at Assemble.  Serial BilinearForm only; AssembleDiagonal (and a
+    Jacobi-preconditioned solve) on such a form raises ECM2_ERR_UNSUPPORTED, as the reference aborts."""
+    kind = CONVECTION
+
+    def __init__(self, coeff, alpha=1.0):
+        self.coeff, self.alpha = coeff, float(alpha)
+
+
 class AssemblyLevel:
     PARTIAL = "partial"
 
@@ -644,6 +658,10 @@ class BilinearForm:
         attribute) the integrator acts on the elements whose attribute a has elem_marker[a-1]."""
         info = self.info()
         kind, data, params = _integrator_args(integ.coeff, self._keep, info["ne"], info["q1d"] ** 3, info["ndofs"])
+        if integ.kind == CONVECTION:  # params[0] = alpha
+            arr = (ctypes.c_double * 1)(integ.alpha)
+            self._keep.append(arr)
+            params = ctypes.cast(arr, ctypes.c_void_p)
         if elem_marker is None:
             _check(_lib.ecm2_pa_form_add_integrator(self._h, integ.kind, kind, data, params))
         else:
@@ -695,6 +713,12 @@ class BilinearForm:
         v = [ctypes.c_int() for _ in range(4)]
         _check(_lib.ecm2_pa_form_boundary_info(self._h, *[ctypes.byref(a) for a in v]))
         return tuple(a.value for a in v)
+
+    def ConvectionInfo(self):
+        """(a ConvectionIntegrator is present, elements kept by the last Assemble, MultTranspose differs from Mult)."""
+        v = [ctypes.c_int() for _ in range(3)]
+        _check(_lib.ecm2_pa_form_convection_info(self._h, *[ctypes.byref(a) for a in v]))
+        return bool(v[0].value), v[1].value, bool(v[2].value)
 
     def BoundaryQData(self, index: int) -> np.ndarray:
         """pa_data of boundary integrator `index` [nbe][q1d^2] (MassIntegrator::AssemblePABoundary's
@@ -791,10 +815,15 @@ class BilinearForm:
     def IntegratorAddMultPA(self, kind, xe, ye, stream=None):
         _check(_lib.ecm2_pa_form_integrator_add_mult(self._h, kind, _dev_ptr(xe), _dev_ptr(ye), _stream(stream)))
 
+    def IntegratorAddMultTransposePA(self, kind, xe, ye, stream=None):
+        """AddMultTransposePA on E-vectors: ye += A_integ^T xe (the plain apply for mass and diffusion)."""
+        _check(_lib.ecm2_pa_form_integrator_add_mult_transpose(self._h, kind, _dev_ptr(xe), _dev_ptr(ye),
+                                                               _stream(stream)))
+
     def qdata(self, kind) -> np.ndarray:
         info = self.info()
         nq = info["q1d"] ** 3
-        nc = (9 if info["layout"] == QLAYOUT_NATIVE9 else 6) if kind == DIFFUSION else 1
+        nc = (9 if info["layout"] == QLAYOUT_NATIVE9 else 6) if kind == DIFFUSION else (3 if kind == CONVECTION else 1)
         out = np.empty((self.fes.ne, nc, nq), np.float64)
         _check(_lib.ecm2_pa_form_get_qdata(self._h, kind, _np_ptr(out), _stream()))
         return out

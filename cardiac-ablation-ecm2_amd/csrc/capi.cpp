@@ -116,6 +116,16 @@ ecm2::CoeffDesc make_coeff(int coeff_kind, const double *data, const double *par
    // with an empty local space passes an empty tensor's null data pointer)
    return c;
 }
+
+// ConvectionIntegrator(vel, alpha): a velocity coefficient (anything else ECM2_ERR_ARG), params[0] = alpha
+void add_convection(ecm2::PAForm &f, int coeff_kind, const double *data, const double *params, const int *marker,
+                    int n_marker)
+{
+   ECM2_VERIFY(coeff_kind == ECM2_COEFF_CONST_VECTOR || coeff_kind == ECM2_COEFF_QUAD_VECTOR, ecm2::ERR_ARG,
+               "a ConvectionIntegrator takes ECM2_COEFF_CONST_VECTOR or ECM2_COEFF_QUAD_VECTOR, not coefficient kind "
+                  << coeff_kind);
+   f.add_convection(make_coeff(coeff_kind, data, nullptr), params ? params[0] : 1.0, marker, n_marker);
+}
 } // namespace
 
 extern "C" {
@@ -419,7 +429,8 @@ int ecm2_pa_form_add_integrator(ecm2_pa_form *f, int integrator, int coeff_kind,
 {
    return guard([&] {
       NEED(f);
-      f->f->add_integrator(integrator, make_coeff(coeff_kind, data, params));
+      if (integrator == ECM2_CONVECTION) { add_convection(*f->f, coeff_kind, data, params, nullptr, 0); }
+      else { f->f->add_integrator(integrator, make_coeff(coeff_kind, data, params)); }
    });
 }
 
@@ -428,8 +439,14 @@ int ecm2_pa_form_add_integrator_marked(ecm2_pa_form *f, int integrator, int coef
 {
    return guard([&] {
       NEED(f); NEED(marker);
-      f->f->add_integrator(integrator, make_coeff(coeff_kind, data, params), marker, n_marker);
+      if (integrator == ECM2_CONVECTION) { add_convection(*f->f, coeff_kind, data, params, marker, n_marker); }
+      else { f->f->add_integrator(integrator, make_coeff(coeff_kind, data, params), marker, n_marker); }
    });
+}
+
+int ecm2_pa_form_convection_info(const ecm2_pa_form *f, int *present, int *n_active, int *transpose_distinct)
+{
+   return guard([&] { NEED(f); f->f->convection_info(present, n_active, transpose_distinct); });
 }
 
 int ecm2_pa_form_set_attributes(ecm2_pa_form *f, const int *attr)
@@ -588,8 +605,8 @@ int ecm2_pa_form_mult(ecm2_pa_form *f, const double *x, double *y, void *stream)
 
 int ecm2_pa_form_mult_transpose(ecm2_pa_form *f, const double *x, double *y, void *stream)
 {
-   // Mass + Diffusion with scalar coefficients is symmetric: A^T x = A x
-   return guard([&] { NEED(f); f->f->mult(x, y, S(stream)); });
+   // the symmetric parts as Mult, plus C^T x of a convection integrator (bitwise the Mult without one)
+   return guard([&] { NEED(f); f->f->mult_transpose(x, y, S(stream)); });
 }
 
 int ecm2_pa_form_add_mult(ecm2_pa_form *f, const double *x, double *y, double a, void *stream)
@@ -618,6 +635,15 @@ int ecm2_pa_form_integrator_add_mult(ecm2_pa_form *f, int integrator, const doub
    return guard([&] {
       NEED(f); NEED(xe); NEED(ye);
       f->f->integrator_add_mult(integrator, xe, ye, S(stream));
+   });
+}
+
+int ecm2_pa_form_integrator_add_mult_transpose(ecm2_pa_form *f, int integrator, const double *xe, double *ye,
+                                               void *stream)
+{
+   return guard([&] {
+      NEED(f); NEED(xe); NEED(ye);
+      f->f->integrator_add_mult(integrator, xe, ye, S(stream), true);
    });
 }
 
@@ -792,6 +818,8 @@ int ecm2_par_form_add_integrator(ecm2_par_form *f, int integrator, int coeff_kin
 {
    return guard([&] {
       NEED(f);
+      ECM2_VERIFY(integrator != ECM2_CONVECTION, ecm2::ERR_UNSUPPORTED,
+                  "a distributed form has no ConvectionIntegrator");
       f->f->local().add_integrator(integrator, make_coeff(coeff_kind, data, params));
    });
 }
@@ -801,6 +829,8 @@ int ecm2_par_form_add_integrator_marked(ecm2_par_form *f, int integrator, int co
 {
    return guard([&] {
       NEED(f); NEED(marker);
+      ECM2_VERIFY(integrator != ECM2_CONVECTION, ecm2::ERR_UNSUPPORTED,
+                  "a distributed form has no ConvectionIntegrator");
       f->f->local().add_integrator(integrator, make_coeff(coeff_kind, data, params), marker, n_marker);
    });
 }

@@ -1,5 +1,5 @@
 // dev_common.hpp -- device-side helpers shared by the gfx950 kernel translation units
-// (k_setup.hip, k_tpe.hip, k_line.hip, k_misc.hip, k_lform.hip, k_bdr.hip).  Included by .hip files only.
+// (k_setup.hip, k_tpe.hip, k_line.hip, k_misc.hip, k_lform.hip, k_bdr.hip, k_conv.hip).  Included by .hip files only.
 #pragma once
 
 #include "kernels.hpp"

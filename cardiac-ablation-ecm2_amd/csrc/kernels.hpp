@@ -1,7 +1,8 @@
 // kernels.hpp -- host launchers for the gfx950 HIP kernels (k_setup.hip: qdata and
 // coefficient setup; k_tpe.hip: thread-per-element p <= 2 apply and diagonal; k_line.hip:
 // line / brick p >= 3 apply and the sum-factorised diagonal; k_misc.hip: workgroup-per-element
-// apply, restriction, vector and solver kernels; k_lform.hip: the linear form's element vectors).
+// apply, restriction, vector and solver kernels; k_lform.hip: the linear form's element vectors;
+// k_bdr.hip: the boundary-face terms; k_conv.hip: the convection term).
 //
 // Quadrature-data layouts (the qdata a PA form owns):
 //  * BLOCKED (fused thread-per-element kernel): elements in blocks of 64 (one
@@ -528,6 +529,39 @@ void bdr_transpose_apply(int D, int Q, int n, const double *qd, bool squared, do
 // y[dof[r]] += sum_{k in off[r] .. off[r + 1]} yf[idx[k]] in ascending k: one thread per boundary dof,
 // no atomics
 void bdr_add(int nrows, const int *dof, const int *off, const int *idx, const double *yf, double *y, hipStream_t s);
+
+// ---- convection (k_conv.hip) ----
+// ConvectionIntegrator at AssemblyLevel::PARTIAL over a compacted list of n active elements (`act`:
+// their element indices, ascending): PAConvectionSetup3D (fem/integ/bilininteg_convection_pa.cpp:
+// 100-152), PAConvectionApply3D / PAConvectionApplyT3D (bilininteg_convection_kernels.hpp:274-451,
+// 897-).  Two layouts of the qdata, the gather rows and the E-vector (conv_plan.hpp):
+//   blocked (p <= 2, thread per element): qd [blk][nq][3][64], map / E-vector [blk][nd][64];
+//   else    (p = 3, 4, sheet per element): qd [k][3][nq] (the reference's), map / E-vector [k][nd].
+struct ConvSetupArgs
+{
+   int n = 0, q1d = 0, blocked = 0;
+   const int *act = nullptr;        // device [n]
+   const double *enodes = nullptr;  // device [ne][3][8] lexicographic corners, or
+   const double *J = nullptr;       // device, MFEM layout NQ x 3 x 3 x NE; exactly one
+   const double *W = nullptr;       // device tensor weights [nq]
+   QPts qp = {};                    // 1D Gauss-Legendre points (corner geometry)
+   double alpha = 1.0;
+   double v[3] = {0, 0, 0};         // a constant velocity, or
+   const double *vq = nullptr;      // device [ne][nq][3] per-point values (caller element order)
+   double *qd = nullptr;
+};
+// qd(q, c, k) = alpha W_q (adj J(q) v(q))_c
+void conv_setup_qdata(const ConvSetupArgs &a, hipStream_t s);
+// (D1D, Q1D) of the convection apply: p = 1..4 with p + 1 or p + 2 points
+bool has_conv_apply(int D, int Q);
+bool conv_blocked(int D);  // the thread-per-element kernel and its layouts (p <= 2)
+// ye = B^T [(qd . grad_ref)(x_e)] (transpose: sum_c G_c^T [qd_c (B x_e)]), x_e gathered through map
+// (entries g, or -1 - g for a minus sign); ye overwritten.  b: the 1D tables as a kernel argument.
+void conv_apply(int D, int Q, bool transpose, int n, const int *map, const double *qd, const double *x, double *ye,
+                const Basis1D &b, hipStream_t s);
+// y[dof[r]] += sum_{k in off[r] .. off[r + 1]} (+/-) ye[idx[k]] in ascending k (idx < 0: minus
+// ye[-1 - idx]): one thread per row, no atomics
+void conv_add(int nrows, const int *dof, const int *off, const int *idx, const double *ye, double *y, hipStream_t s);
 
 // ---- ElementRestriction ----
 void restriction_mult(long n, int nd, const int *gmap_native, const double *x, double *xe,

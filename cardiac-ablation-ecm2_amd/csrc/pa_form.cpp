@@ -22,7 +22,8 @@ void require_device()
 }
 
 PAForm::PAForm(int ne, int order, int ndofs, const int *gather_map_host, int q1d, int n_owned)
-   : ne_(ne), order_(order), ndofs_(ndofs), n_owned_(n_owned < 0 ? ndofs : n_owned), bdr_(order, ndofs)
+   : ne_(ne), order_(order), ndofs_(ndofs), n_owned_(n_owned < 0 ? ndofs : n_owned), bdr_(order, ndofs),
+     conv_(ne, order, q1d > 0 ? q1d : default_q1d(order), ndofs)
 {
    ECM2_VERIFY(n_owned_ <= ndofs, ERR_ARG, "n_owned > ndofs");
    ECM2_VERIFY(ne >= 0 && ndofs >= 0, ERR_ARG, "negative sizes");
@@ -170,6 +171,20 @@ void PAForm::add_integrator(int kind, const CoeffDesc &c, const int *marker, int
    assembled_ = false;
 }
 
+void PAForm::add_convection(const CoeffDesc &c, double alpha, const int *marker, int n_marker)
+{
+   ECM2_VERIFY(n_owned_ == ndofs_, ERR_UNSUPPORTED, "a distributed local form has no convection integrator");
+   conv_.set(c, alpha, marker, n_marker);
+   assembled_ = false;
+}
+
+void PAForm::convection_info(int *present, int *n_active, int *transpose_distinct) const
+{
+   if (present) { *present = conv_.present() ? 1 : 0; }
+   if (n_active) { *n_active = conv_.n_active(); }
+   if (transpose_distinct) { *transpose_distinct = conv_.n_active() > 0 ? 1 : 0; }
+}
+
 void PAForm::set_boundary(int nbe, const int *bdr_map_host, const int *bdr_attr_host, const double *bdr_nodes_host, int q1d)
 {
    ECM2_VERIFY(n_owned_ == ndofs_, ERR_UNSUPPORTED, "a distributed local form has no boundary integrators");
@@ -269,6 +284,16 @@ void PAForm::assemble(hipStream_t s)
    setup_marker_diagonal(s);
    build_launch_args();
    if (bdr_.has_boundary()) { bdr_.assemble_mass(s); }  // face qdata and the add pass's CSR
+   if (conv_.present())
+   {
+      // the active elements' rows, the add pass's CSR and the qdata from the live velocity
+      ConvGeometry g;
+      g.enodes = enodes_.data();
+      g.J = jac_;
+      g.W = W_.data();
+      g.qp = qp_;
+      conv_.assemble(gmap_host_, attr_, g, basis_, s);
+   }
    assembled_ = true;
    gen_++;
 }
@@ -629,6 +654,19 @@ void PAForm::mult(const double *x, double *y, hipStream_t s)
    // the boundary block of PABilinearFormExtension::Mult (bilinearform_ext.cpp:625-675), after the
    // volume result is complete (partial scatter: after finish_shared), whatever kernel computed it
    if (has_boundary_integrators()) { bdr_.add_mult(x, y, s); }
+   // then the convection term: one apply into its E-vector and a fixed-order add (conv_term.hpp)
+   if (has_convection()) { conv_.add_mult(x, y, false, s); }
+}
+
+void PAForm::mult_transpose(const double *x, double *y, hipStream_t s)
+{
+   ECM2_VERIFY(assembled_, ERR_STATE, "MultTranspose before Assemble");
+   ECM2_VERIFY(ndofs_ == 0 || (x && y), ERR_ARG, "null vector");
+   if (ndofs_ == 0) { return; }
+   // Mass, Diffusion and the boundary mass are symmetric: their transposes are the Mult, launch for launch
+   mult_volume(x, y, s);
+   if (has_boundary_integrators()) { bdr_.add_mult(x, y, s); }
+   if (has_convection()) { conv_.add_mult(x, y, true, s); }
 }
 
 void PAForm::mult_volume(const double *x, double *y, hipStream_t s)
@@ -680,7 +718,8 @@ int PAForm::energy_parts() const
                    layout_.tsnap && have_diff_ && D_ == 3 && Q_ == 4;
    // (a boundary integrator: the folded sum would miss d^T H d of the face term, so the caller runs
    // the dot pass over the complete Mult)
-   return ts && ndofs_ > 0 && !has_boundary_integrators() ? (layout_.nblk() + 3) / 4 : 0;
+   // (a convection integrator likewise: x^T C x is not in the folded sum)
+   return ts && ndofs_ > 0 && !has_boundary_integrators() && !has_convection() ? (layout_.nblk() + 3) / 4 : 0;
 }
 
 void PAForm::mult_energy(const double *x, double *y, double *en, hipStream_t s)
@@ -823,6 +862,11 @@ void PAForm::apply_blocks(const double *x, const double *xg, double *y, double *
 void PAForm::assemble_diagonal(double *diag, hipStream_t s)
 {
    ECM2_VERIFY(assembled_, ERR_STATE, "AssembleDiagonal before Assemble");
+   // ConvectionIntegrator::AssembleDiagonalPA aborts (bilininteg_convection_pa.cpp:216-227); a term whose
+   // marker keeps no element contributes nothing and is let through
+   ECM2_VERIFY(!(has_convection() && conv_.n_active() > 0), ERR_UNSUPPORTED,
+               "AssembleDiagonal is not implemented for a form with a ConvectionIntegrator (so neither is a "
+               "Jacobi-preconditioned solve on it): keep the convection out of the implicit operator");
    if (ndofs_ == 0) { return; }
    // The diagonal is a function of the assembled state alone (every setter clears assembled_, and
    // Assemble bumps gen_): repeated requests between two Assembles -- a Jacobi smoother per PCG
@@ -964,9 +1008,15 @@ void PAForm::restriction_mult_transpose(const double *xe, double *y, hipStream_t
    kern::restriction_mult_transpose(ndofs_, ND_, csr_off_.data(), csr_idx_.data(), xe, y, s);
 }
 
-void PAForm::integrator_add_mult(int kind, const double *xe, double *ye, hipStream_t s)
+void PAForm::integrator_add_mult(int kind, const double *xe, double *ye, hipStream_t s, bool transpose)
 {
    ECM2_VERIFY(assembled_, ERR_STATE, "AddMultPA before Assemble");
+   if (kind == INTEG_CONVECTION)
+   {
+      ECM2_VERIFY(has_convection(), ERR_ARG, "integrator " << kind << " not present");
+      conv_.add_mult_evec(xe, ye, transpose, s);
+      return;
+   }
    ECM2_VERIFY((kind == INTEG_MASS && have_mass_) || (kind == INTEG_DIFFUSION && have_diff_),
                ERR_ARG, "integrator " << kind << " not present");
    ApplyArgs a = apply_args(xe, nullptr, ye, nullptr, 0, layout_.nblk(), qdata());
@@ -986,6 +1036,12 @@ void PAForm::integrator_add_mult(int kind, const double *xe, double *ye, hipStre
 void PAForm::get_qdata(int kind, double *out, hipStream_t s)
 {
    ECM2_VERIFY(assembled_, ERR_STATE, "get_qdata before Assemble");
+   if (kind == INTEG_CONVECTION)
+   {
+      ECM2_VERIFY(has_convection(), ERR_ARG, "integrator " << kind << " not present");
+      conv_.get_qdata(out, s);  // [ne][3][nq], zeros on the elements its marker excludes
+      return;
+   }
    const bool diff = kind == INTEG_DIFFUSION;
    ECM2_VERIFY(diff ? have_diff_ : have_mass_, ERR_ARG, "integrator " << kind << " not present");
    DeviceArray<double> fd, fm;

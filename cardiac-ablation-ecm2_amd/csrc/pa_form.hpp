@@ -1,5 +1,5 @@
 // pa_form.hpp -- MI355X PA form: the drop-in for the reference's
-// BilinearForm(PARTIAL) + {MassIntegrator(alpha), DiffusionIntegrator(beta)}
+// BilinearForm(PARTIAL) + {MassIntegrator(alpha), DiffusionIntegrator(beta)[, ConvectionIntegrator(v, a)]}
 // and its PABilinearFormExtension.
 //
 // Reference interface mirrored:
@@ -23,6 +23,7 @@
 
 #include "bdr_term.hpp"
 #include "common.hpp"
+#include "conv_term.hpp"
 #include "fe.hpp"
 #include "kernels.hpp"
 #include "plan_dev.hpp"
@@ -51,7 +52,7 @@ enum ScatterMode : int
    SCATTER_ATOMIC = 1     // FP64 atomic adds into a zeroed y
 };
 
-enum IntegratorKind : int { INTEG_MASS = 0, INTEG_DIFFUSION = 1 };
+enum IntegratorKind : int { INTEG_MASS = 0, INTEG_DIFFUSION = 1, INTEG_CONVECTION = 2 };
 
 // The CSR transpose of a gather map [ne][nd] (ElementRestriction's offsets / indices,
 // restriction.cpp:68-106; index -1 - lid = minus sign) that kern::restriction_mult_transpose sums:
@@ -132,6 +133,17 @@ public:
    // whose attribute a has a > 0 and marker[a - 1] != 0 only (AddMultWithMarkers,
    // bilinearform_ext.cpp:753-774,807-847); the attributes come from set_attributes.
    void add_integrator(int kind, const CoeffDesc &c, const int *marker = nullptr, int n_marker = 0);
+   // BilinearForm::AddDomainIntegrator(new ConvectionIntegrator(vel, alpha)[, elem_marker]) (conv_term.hpp):
+   // c a velocity (COEFF_CONST_VECTOR / COEFF_QUAD_VECTOR, anything else ERR_ARG); at most one per form; the
+   // form's rule must be p + 1 or p + 2 points with p = 1..4 (ConvectionIntegrator's specialisations,
+   // bilininteg_convection_pa.cpp:30-58; its GetRule is the form's default p + 2), else ERR_UNSUPPORTED; a
+   // distributed local form (n_owned < ndofs) refuses it.  Mult then adds C x after the volume part and the
+   // boundary term, mult_transpose C^T x; the diagonal is refused as the reference's AssembleDiagonalPA aborts
+   // (bilininteg_convection_pa.cpp:216-227) and the Mult's energy is not folded (energy_parts() = 0).
+   void add_convection(const CoeffDesc &c, double alpha, const int *marker = nullptr, int n_marker = 0);
+   bool has_convection() const { return conv_.present(); }
+   // (present, active elements of the last Assemble, MultTranspose differs from Mult)
+   void convection_info(int *present, int *n_active, int *transpose_distinct) const;
    // element attributes (host [ne], caller element order), as Mesh::GetAttribute
    void set_attributes(const int *attr_host);
    // Boundary integrators (BilinearForm::AddBoundaryIntegrator(new MassIntegrator(h), bdr_marker):
@@ -162,6 +174,9 @@ public:
 
    // y = A x (BilinearForm::Mult semantics: y overwritten).
    void mult(const double *x, double *y, hipStream_t s);
+   // y = A^T x (PABilinearFormExtension::MultTranspose, bilinearform_ext.cpp:679-): the symmetric volume and
+   // boundary parts as Mult, then C^T x of a convection integrator
+   void mult_transpose(const double *x, double *y, hipStream_t s);
    // y += a A x (Operator::AddMult, linalg/operator.hpp:87-92): Mult into a form-owned work
    // vector, then one axpy.  Like every call on a form (the reference's Mult reuses its
    // localX / localY too, bilinearform_ext.hpp:75), AddMult is stream-serial per form: two calls
@@ -201,7 +216,8 @@ public:
    // Reference-shaped pieces (E-vector layout [e][nd], lexicographic).
    void restriction_mult(const double *x, double *xe, hipStream_t s);
    void restriction_mult_transpose(const double *xe, double *y, hipStream_t s);
-   void integrator_add_mult(int kind, const double *xe, double *ye, hipStream_t s);
+   // (transpose: AddMultTransposePA -- the plain apply for the symmetric mass and diffusion)
+   void integrator_add_mult(int kind, const double *xe, double *ye, hipStream_t s, bool transpose = false);
    // qdata in the reference's native layout, copied to the host.
    void get_qdata(int kind, double *out_host, hipStream_t s);
 
@@ -260,6 +276,7 @@ private:
 
    int ne_, order_, ndofs_, n_owned_, D_, Q_, ND_, NQ_;
    BoundaryTerm bdr_;               // boundary integrators (empty unless set_boundary was called)
+   ConvectionTerm conv_;            // the convection integrator (empty unless add_convection was called)
    DofToQuad maps_;
    QPts qp_ = {};                   // maps_.qpts as a kernel argument
    Basis1D basis_, basis1_;

@@ -36,6 +36,31 @@ extern "C" {
 /* Integrator kinds (MassIntegrator, DiffusionIntegrator: fem/bilininteg.hpp:2177-2465). */
 #define ECM2_MASS 0
 #define ECM2_DIFFUSION 1
+/* ConvectionIntegrator(vel, alpha) (fem/bilininteg.hpp; PA: fem/integ/bilininteg_convection_pa.cpp): the
+ * blood-flow advection rho_b c_b u . grad T of the bioheat operator, on the serial ecm2_pa_form.
+ *   Setup   PAConvectionSetup3D (bilininteg_convection_pa.cpp:100-152): pa_data(q, c, e) =
+ *           alpha W_q (adj J(q) v(q))_c, three values per point, reference layout [e][3][nq].
+ *   Rule    ConvectionIntegrator::GetRule (fem/bilininteg.cpp:1610-1623, fem/eltrans.cpp:477-523): order
+ *           2p + 2 on a trilinear hex = p + 2 points per direction, the form's default.  The form's rule
+ *           must be p + 1 or p + 2 points with p = 1..4 (the reference's specialisations,
+ *           bilininteg_convection_pa.cpp:30-58); otherwise add_integrator returns ECM2_ERR_UNSUPPORTED.
+ *   Apply   PAConvectionApply3D (bilininteg_convection_kernels.hpp:274-451): y_e += B^T [(pa . grad_ref) x_e];
+ *           transpose PAConvectionApplyT3D (:897-): y_e += sum_c G_c^T [pa_c (B x_e)].
+ *   Coefficient: ECM2_COEFF_CONST_VECTOR (host data[3]) or ECM2_COEFF_QUAD_VECTOR (device [ne][nq][3], the
+ *           velocity projected at the rule's points); params[0] = alpha, NULL = 1; any other kind is
+ *           ECM2_ERR_ARG.  The qdata is built at assemble from the live array (assemble-time semantics).
+ *   Markers (ecm2_pa_form_add_integrator_marked): the term acts on the marked attributes only (the fluid
+ *           domain); only those active elements are stored and launched, a term with none launches nothing.
+ *   Mult = volume part, boundary term, then C x: one apply into an E-vector over the active elements and a
+ *           fixed-order add pass (no atomics; two Mults are bitwise equal).  ecm2_pa_form_mult_transpose
+ *           adds C^T x instead.  AddMult, the ecm2_operator wrapper and the ODE steps follow.
+ *   Diagonal: the reference aborts (AssembleDiagonalPA, bilininteg_convection_pa.cpp:216-227);
+ *           ecm2_pa_form_assemble_diagonal returns ECM2_ERR_UNSUPPORTED on a form whose convection
+ *           integrator has an active element, and so does ecm2_pcg_solve(jacobi = 1) on it.  Put the
+ *           convection in the explicit operator K of ecm2_ode_step only: T = M + c dt K_sym stays symmetric.
+ *   ecm2_pa_form_energy_parts is 0 for such a form.  At most one per form (a second: ECM2_ERR_UNSUPPORTED);
+ *   distributed forms (ecm2_par_form_add_integrator[_marked]) return ECM2_ERR_UNSUPPORTED. */
+#define ECM2_CONVECTION 2
 
 /* Coefficient kinds (CoefficientVector COMPRESSED storage, fem/coefficient.cpp:2006-2180). */
 #define ECM2_COEFF_CONSTANT 0       /* ConstantCoefficient                                   */
@@ -247,6 +272,10 @@ int ecm2_pa_form_add_integrator(ecm2_pa_form *f, int integrator, int coeff_kind,
  * operator, no extra pass per Mult).  Needs ecm2_pa_form_set_attributes before assemble. */
 int ecm2_pa_form_add_integrator_marked(ecm2_pa_form *f, int integrator, int coeff_kind, const double *data,
                                        const double *params, const int *marker, int n_marker);
+/* Introspection of a ConvectionIntegrator (any output may be NULL): *present 1 when the form has one;
+ * *n_active the elements kept by the last assemble; *transpose_distinct 1 when MultTranspose differs
+ * from Mult (an active convection term). */
+int ecm2_pa_form_convection_info(const ecm2_pa_form *f, int *present, int *n_active, int *transpose_distinct);
 /* Element attributes of the form's elements (the mesh's, host [ne], caller element order). */
 int ecm2_pa_form_set_attributes(ecm2_pa_form *f, const int *attr);
 /* Robin boundaries: BilinearForm::AddBoundaryIntegrator(new MassIntegrator(h)[, bdr_marker]) at
@@ -328,8 +357,9 @@ int ecm2_pa_form_assemble(ecm2_pa_form *f, void *stream);
  * bilinearform_ext.cpp:487-564): y = A x, y overwritten.  x, y device [ndofs]. */
 int ecm2_pa_form_mult(ecm2_pa_form *f, const double *x, double *y, void *stream);
 /* PABilinearFormExtension::MultTranspose (bilinearform_ext.hpp:99, bilinearform_ext.cpp:
- * 679-): y = A^T x.  Mass + Diffusion with scalar coefficients are symmetric, so this is
- * the Mult (tests/test_gpu_parity.py asserts the equality). */
+ * 679-): y = A^T x.  Mass, Diffusion and the boundary mass are symmetric, so without a
+ * ConvectionIntegrator this is the Mult, launch for launch (tests/test_gpu_parity.py asserts the
+ * equality); with one, the volume and boundary parts as Mult plus C^T x (PAConvectionApplyT3D). */
 int ecm2_pa_form_mult_transpose(ecm2_pa_form *f, const double *x, double *y, void *stream);
 /* Operator::AddMult (linalg/operator.hpp:108-109): y += a A x. */
 int ecm2_pa_form_add_mult(ecm2_pa_form *f, const double *x, double *y, double a, void *stream);
@@ -341,7 +371,12 @@ int ecm2_pa_form_restriction_mult_transpose(ecm2_pa_form *f, const double *xe, d
 /* BilinearFormIntegrator::AddMultPA (bilininteg.hpp:49-97): ye += A_integ xe (E-vectors). */
 int ecm2_pa_form_integrator_add_mult(ecm2_pa_form *f, int integrator, const double *xe,
                                      double *ye, void *stream);
-/* pa_data in the reference layout (diffusion [ne][6][nq], mass [ne][nq]), host out. */
+/* BilinearFormIntegrator::AddMultTransposePA (bilininteg.hpp:49-97): ye += A_integ^T xe.  For the
+ * symmetric mass and diffusion it is the plain apply. */
+int ecm2_pa_form_integrator_add_mult_transpose(ecm2_pa_form *f, int integrator, const double *xe,
+                                               double *ye, void *stream);
+/* pa_data in the reference layout (diffusion [ne][6][nq], mass [ne][nq], convection [ne][3][nq] with
+ * zeros on the elements its marker excludes), host out. */
 int ecm2_pa_form_get_qdata(ecm2_pa_form *f, int integrator, double *out, void *stream);
 int ecm2_pa_form_info(const ecm2_pa_form *f, int *ne, int *ndofs, int *d1d, int *q1d,
                       int *kernel, int *layout);
