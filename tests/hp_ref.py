@@ -21,7 +21,9 @@ one quadrature point is hundreds of units.
 C and C_DIAG are the bounds of the device tests: 4 * c_ref rounded up to a power of two, where c_ref
 is the worst constant of the CPU oracle over the case matrix -- of its two independent Mult evaluations
 (PA and element-matrix) for C, of its diagonal for C_DIAG (tests/test_hp_reference.py measures both and
-checks the constants against them; DESIGN.md "Tolerance" has the tables and the reasoning).
+checks the constants against them; DESIGN.md "Tolerance" has the tables and the reasoning).  C_CONV and
+C_CONV_QD are the same rule for the convection term's products and its qdata, whose reference and bound
+live in tests/conv_ref.py (measured by tests/test_conv_reference.py).
 """
 import numpy as np
 
@@ -41,6 +43,14 @@ C = 64.0
 # p = 4.  One bound for both would be 256 for the Mult too, above the 190 - 620 units of a 1e-12
 # relative error at one quadrature point, which the Mult bound must see.
 C_DIAG = 256.0
+# The convection term (tests/conv_ref.py: S and Pabs over the edge-form |J|; tests/test_conv_reference.py measures
+# both).  Mult and MultTranspose jointly: c_ref = 4.13 (the float64 checker's dense element matrices, perturbed
+# 5 x 4 x 3, p = 1, Q = 2), 4 * c_ref = 16.5 -> 32.  The chains are those of the volume Mult with one qdata
+# factor per point instead of a 3 x 3 product.
+C_CONV = 32.0
+# Its qdata alpha W adj(J) v against Pabs: c_ref = 7.14 (perturbed, p = 4, Q = 6), 4 * c_ref = 28.6 -> 32: two
+# roundings per Jacobian entry, a difference of two products per cofactor, three terms and two scalings.
+C_CONV_QD = 32.0
 
 
 def _oracle():

@@ -4,6 +4,12 @@ against the oracle's volume operator plus the numpy restatement of the reference
 relerr < helpers.RTOL (1e-12, the project's parity bar); x is uniform random in [0, 1), the parity tests'
 non-cancelling input; y is preset to NaN (Mult overwrites).
 
+This file is the coverage of the paths and the ABI: every volume kernel mode and scatter behind the term,
+the E-vector entry points, determinism, the Assemble-time state, the wrapper, the refusals and the
+example.  The tight bar -- C x, C^T x and the qdata componentwise against an extended-precision reference,
+on the temperature fields the solver applies the operator to, and the Jacobian geometry -- is
+tests/test_gpu_convection_componentwise.py's.
+
 Meshes, the smallest at which each path can go wrong: 2 x 1 x 1 (fewer elements than a wave or a sheet
 group), 5 x 4 x 3 with every vertex moved (60 non-affine elements: one partial wave), fichera refined once
 (56 elements, unstructured sharing), and 8 x 8 x 8 (1 x 0.7 x 1.3, structured numbering) whose marker
@@ -20,6 +26,7 @@ import ecm2_amd as E
 import oracle as O
 import bdr_ref as BR
 import conv_ref as R
+from conv_cases import cube8_attributes
 from helpers import ROOT, RTOL, relerr
 
 pytestmark = pytest.mark.gpu
@@ -51,17 +58,6 @@ def host(t):
 def modes(p):
     """Every volume kernel mode the order allows (the default rule p + 2)."""
     return ([E.KERNEL_TPE] if p <= 2 else []) + [E.KERNEL_LINE, E.KERNEL_WPE, E.KERNEL_UNFUSED]
-
-
-def cube8_attributes():
-    """8 x 8 x 8, lexicographic elements: attribute 2 on the z layers 1, 2, 3, 5, 6 (320 elements), 3 on
-    the first 27 elements of layer 7, 1 elsewhere."""
-    e = np.arange(512)
-    iz, r = e // 64, e % 64
-    attr = np.ones(512, np.int32)
-    attr[np.isin(iz, [1, 2, 3, 5, 6])] = 2
-    attr[(iz == 7) & (r < 27)] = 3
-    return attr
 
 
 _MESH, _SPACES, _REFS, _CX = {}, {}, {}, {}

@@ -1,8 +1,9 @@
 """GPU tests of the sourced implicit step M du/dt = -K u + b (ecm2_ode_step_source) with b assembled
 by the device linear form: against the oracle's stepping (the setup of
 tests/test_solvers.py::test_ode_step_matches_oracle and its bound for the same kind of comparison),
-the null source, the uniform-heating closed form of examples/rf_heat_step.cpp, and a loopback-group
-operator."""
+the null source, the uniform-heating closed form of examples/rf_heat_step.cpp, a loopback-group
+operator, and the step whose explicit operator K carries a ConvectionIntegrator (non-symmetric K, symmetric
+T) against the same stepping with the numpy checker of the term (tests/conv_ref.py)."""
 import numpy as np
 import pytest
 
@@ -11,6 +12,7 @@ import ecm2_amd as E
 import oracle as O
 import ode as ODE
 import lform_ref as R
+import conv_ref as CR
 from helpers import coeff_function, nonaligned, relerr
 
 pytestmark = pytest.mark.gpu
@@ -164,6 +166,79 @@ def test_sourced_step_matches_oracle(ode_type):
     assert np.array_equal(uh[ess], u0[ess])
     err = relerr(uh - u0, ur - u0)
     print(f"type {ode_type}: {err:.2e}")
+    assert err < 1e-9
+
+
+_CONV = {}
+
+
+def _convective(order):
+    """The setup above with a mesh of its own carrying the attributes 1 + e mod 3, and the numpy checker of
+    the convection term with the per-point reference velocity (y, -x, x): computed once per order."""
+    if order not in _CONV:
+        m = _mesh("cart")
+        m.SetAttributes(1 + (np.arange(m.GetNE()) % 3).astype(np.int32))
+        fes = E.H1Space(m, order)
+        conv = CR.ConvRef(order, O.default_q1d(order), fes.gather_map(), fes.ndofs, m.element_nodes())
+        keep = CR.marker_keep(m.GetAttributes(), CONV_MARKER)
+        assert 0 < keep.sum() < fes.ne
+        _CONV[order] = (m, fes, conv, CR.reference_velocity(conv.P), keep)
+    return _CONV[order]
+
+
+CONV_MARKER = [0, 1, 1]
+CONV_ALPHA = 1.7
+
+
+@pytest.mark.parametrize("ode_type,order,sourced", [(t, 2, False) for t in TYPES] + [(23, 3, False), (22, 2, True)])
+def test_step_with_convection_in_K_matches_oracle(ode_type, order, sourced):
+    """The non-symmetric explicit operator: T = M_alpha + c dt K_beta stays symmetric, K = K_beta +
+    Convection(per-point velocity, marked) -- two steps against oracle/ode.py's step with the closure
+    rhs = -(K_beta u + C u) [+ b], rhs[ess] = 0, C u from tests/conv_ref.py.  Order 3 steps the sheet
+    kernel, order 2 the thread-per-element one; the bar, the bitwise essential values and the stage-solve
+    counts are those of test_sourced_step_matches_oracle."""
+    import torch
+    m, fes, conv, v, keep = _convective(order)
+    dt = 0.05
+    c = E.ode_implicit_coeff(ode_type)
+    T = _serial(m, fes, order, _alpha, _beta, scale_beta=c * dt)
+    P = O.quad_points(m.element_nodes(), O.default_q1d(order))
+    Kf = E.BilinearForm(fes)
+    Kf.AddDomainIntegrator(E.ConvectionIntegrator(E.VectorCoefficient(torch.as_tensor(v).cuda()), CONV_ALPHA), CONV_MARKER)
+    K = _quad_form(Kf, fes.ne, P, None, _beta, 1.0)
+    assert K.ConvectionInfo() == (True, int(keep.sum()), True)
+    Tr = _oracle(m, fes, order, _alpha, _beta, scale_beta=c * dt)
+    Kr = _oracle(m, fes, order, None, _beta)
+    ess = fes.boundary_dofs()
+    X = fes.dof_coords()
+    u0 = 37.0 + 20.0 * np.exp(-4.0 * np.sum((X - 0.5) ** 2, axis=1))
+    # (any frozen true-dof vector serves as the source: a smooth load through the oracle's mass)
+    bh = _oracle(m, fes, order, _alpha, None).mult(40.0 * np.cos(3.0 * X[:, 0])) if sourced else None
+
+    def solve(us):
+        rhs = -(Kr.mult(us) + conv.mult(v, us, CONV_ALPHA, keep))
+        if sourced:
+            rhs += bh
+        rhs[ess] = 0.0
+        return Tr.pcg(rhs, ess, rel_tol=1e-13, max_iter=5000)[0]
+
+    ur = u0.copy()
+    for _ in range(2):
+        ur = ODE.step(ode_type, solve, ur, dt)
+    u = torch.as_tensor(u0).cuda()
+    essd = torch.as_tensor(ess).cuda()
+    kw = {"source": torch.as_tensor(bh).cuda()} if sourced else {}
+    for _ in range(2):
+        ns, it, conv_ok = E.ode_step(ode_type, E.Operator(T), E.Operator(K), dt, u, ess=essd, rel_tol=1e-13,
+                                     max_iter=5000, **kw)
+        assert conv_ok and ns == {21: 1, 32: 1, 22: 2, 33: 2, 23: 3, 34: 3}[ode_type]
+    uh = u.cpu().numpy()
+    assert np.array_equal(uh[ess], u0[ess])
+    # the term is not a bystander: its share of the first slope's right-hand side is far above the bar
+    share = np.abs(conv.mult(v, u0, CONV_ALPHA, keep)).max() / np.abs(Kr.mult(u0)).max()
+    err = relerr(uh - u0, ur - u0)
+    print(f"type {ode_type} p={order} source={sourced}: {err:.2e} (|C u0| / |K u0| = {share:.2e})")
+    assert share > 1e-3
     assert err < 1e-9
 
 
