@@ -13,6 +13,7 @@ benchmark read like the reference's own drivers:
     AddDomainIntegrator(MassIntegrator(Q))             AddDomainIntegrator(MassIntegrator(Q))
     Assemble / Mult / AssembleDiagonal                 Assemble / Mult / AssembleDiagonal
     ConstrainedOperator + CGSolver (+ Jacobi)          BilinearForm.PCG
+    ConstrainedOperator + BiCGSTABSolver (+ Jacobi)    Operator.BiCGSTAB
 
 Vectors are torch CUDA float64 tensors (torch is plumbing: device memory and
 streams).  There is no CPU fallback: without the built library or without a GPU
@@ -938,6 +939,16 @@ _PAR_SIGS = {
                                             ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                             ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                             ctypes.c_void_p]),
+    "ecm2_operator_bicgstab": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double,
+                                              ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                              ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]),
+    "ecm2_bicgstab_last_converged": (ctypes.c_int, []),
+    "ecm2_ode_step_bicgstab": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                              ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                              ctypes.c_void_p]),
     "ecm2_operator_destroy": (None, [ctypes.c_void_p]),
     "ecm2_linear_form_default_q1d": (ctypes.c_int, [ctypes.c_int]),
     "ecm2_linear_form_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
@@ -1283,6 +1294,28 @@ class Operator:
                                             ctypes.byref(it), ctypes.byref(nrm), _stream(stream)))
         return it.value, nrm.value
 
+    def BiCGSTAB(self, b, x, ess=None, rel_tol=1e-12, abs_tol=0.0, max_iter=1000, jacobi_of=None, stream=None):
+        """ConstrainedOperator(DIAG_ONE) + BiCGSTABSolver (linalg/solvers.cpp:1579-1805) for a nonsymmetric
+        operator; jacobi_of: the Operator whose diagonal OperatorJacobiSmoother takes (the symmetric part of a
+        form with a ConvectionIntegrator, whose own diagonal is refused), None: no preconditioner.
+        Returns (iters, final_norm), final_norm = the last ||s|| or ||r||; bicgstab_last_converged() tells
+        whether it converged."""
+        it, nrm = ctypes.c_int(), ctypes.c_double()
+        n_ess = 0 if ess is None else int(ess.numel())
+        if jacobi_of is not None and not isinstance(jacobi_of, Operator):
+            raise ECM2Error("jacobi_of must be an Operator")
+        _check(_par_lib().ecm2_operator_bicgstab(self._h, jacobi_of._h if jacobi_of is not None else None,
+                                                 _dev_ptr(ess) if n_ess else None, n_ess, _dev_ptr(b), _dev_ptr(x),
+                                                 rel_tol, abs_tol, max_iter, ctypes.byref(it), ctypes.byref(nrm),
+                                                 _stream(stream)))
+        return it.value, nrm.value
+
+
+def bicgstab_last_converged() -> bool:
+    """IterativeSolver::GetConverged() of this thread's last Operator.BiCGSTAB: False after the rho_1 == 0
+    and omega == 0 stops and at max_iter."""
+    return bool(_par_lib().ecm2_bicgstab_last_converged())
+
 
 ODE_BACKWARD_EULER, ODE_SDIRK23_L, ODE_SDIRK33, ODE_IMPLICIT_MIDPOINT, ODE_SDIRK23, ODE_SDIRK34 = 21, 22, 23, 32, 33, 34
 
@@ -1296,14 +1329,32 @@ def ode_implicit_coeff(ode_type: int) -> float:
 
 
 def ode_step(ode_type: int, T: Operator, K: Operator, dt: float, u, ess=None, rel_tol=1e-10, max_iter=500,
-             jacobi=True, stream=None, source=None):
+             jacobi=True, stream=None, source=None, solver="pcg", jacobi_of=None):
     """One implicit step of M du/dt = -K u (ex16 ConductionOperator, slope form) on device vector u
     (in place).  T must be M + c dt K with c = ode_implicit_coeff(ode_type).
     source: a device true-dof vector b in the operators' numbering (e.g. LinearForm.Assemble's),
     frozen over the step: M du/dt = -K u + b (ecm2_ode_step_source).
-    Returns (stage solves, total PCG iterations, converged)."""
+    solver: "pcg" (the default: symmetric T, `jacobi` its preconditioner switch) or "bicgstab"
+    (ecm2_ode_step_bicgstab): T = M + c dt (K_sym + C) and K = K_sym + C carry the ConvectionIntegrator, and
+    jacobi_of = the Operator of M + c dt K_sym gives the Jacobi preconditioner (None: none).
+    Returns (stage solves, total solver iterations, converged)."""
     ns, it, conv = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     n_ess = 0 if ess is None else int(ess.numel())
+    if solver not in ("pcg", "bicgstab"):
+        raise ECM2Error(f"unknown stage solver {solver!r}")
+    if solver == "bicgstab":
+        if jacobi_of is not None and not isinstance(jacobi_of, Operator):
+            raise ECM2Error("jacobi_of must be an Operator")
+        if source is not None:
+            _check_field(_OdeSource(), source, T.size)
+        _check(_par_lib().ecm2_ode_step_bicgstab(ode_type, T._h, jacobi_of._h if jacobi_of is not None else None,
+                                                 K._h, _dev_ptr(source), dt, _dev_ptr(u),
+                                                 _dev_ptr(ess) if n_ess else None, n_ess, rel_tol, max_iter,
+                                                 ctypes.byref(ns), ctypes.byref(it), ctypes.byref(conv),
+                                                 _stream(stream)))
+        return ns.value, it.value, bool(conv.value)
+    if jacobi_of is not None:
+        raise ECM2Error("jacobi_of goes with solver=\"bicgstab\"")
     if source is None:
         _check(_par_lib().ecm2_ode_step(ode_type, T._h, K._h, dt, _dev_ptr(u), _dev_ptr(ess) if n_ess else None,
                                         n_ess, rel_tol, max_iter, 1 if jacobi else 0, ctypes.byref(ns),

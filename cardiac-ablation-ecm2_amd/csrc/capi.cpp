@@ -48,6 +48,7 @@ namespace
 {
 thread_local std::string g_last_error;
 thread_local int g_pcg_converged = 0;  // IterativeSolver::GetConverged() of the thread's last PCG
+thread_local int g_bicgstab_converged = 0;  // ... of the thread's last BiCGSTAB
 
 template <typename F>
 int guard(F &&fn)
@@ -1105,6 +1106,41 @@ int ecm2_ode_step(int type, ecm2_operator *T, ecm2_operator *K, double dt, doubl
 {
    return ecm2_ode_step_source(type, T, K, nullptr, dt, u, ess, n_ess, rel_tol, max_iter, jacobi, solves, iterations,
                                converged, stream);
+}
+
+// ---- BiCGSTABSolver (linalg/solvers.cpp:1579-1805) ----
+int ecm2_bicgstab_last_converged(void) { return g_bicgstab_converged; }
+
+int ecm2_operator_bicgstab(ecm2_operator *A, ecm2_operator *jacobi_of, const int *ess, int n_ess, const double *b,
+                           double *x, double rel_tol, double abs_tol, int max_iter, int *iterations,
+                           double *final_norm, void *stream)
+{
+   return guard([&] {
+      NEED(A); NEED(b); NEED(x);
+      g_bicgstab_converged = 0;
+      ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
+      const ecm2::PCGResult r = ecm2::bicgstab_solve(*A->op, jacobi_of ? jacobi_of->op.get() : nullptr, ess, n_ess, b, x,
+                                                     rel_tol, abs_tol, max_iter, S(stream));
+      if (iterations) { *iterations = r.iterations; }
+      if (final_norm) { *final_norm = r.final_norm; }
+      g_bicgstab_converged = r.converged ? 1 : 0;
+   });
+}
+
+int ecm2_ode_step_bicgstab(int type, ecm2_operator *T, ecm2_operator *jacobi_of, ecm2_operator *K, const double *b,
+                           double dt, double *u, const int *ess, int n_ess, double rel_tol, int max_iter, int *solves,
+                           int *iterations, int *converged, void *stream)
+{
+   return guard([&] {
+      NEED(T); NEED(K); NEED(u);
+      ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
+      const ecm2::StepStats st = ecm2::ode_step(type, *T->op, *K->op, dt, u, ess, n_ess, rel_tol, max_iter, false,
+                                                S(stream), b, ecm2::STAGE_BICGSTAB,
+                                                jacobi_of ? jacobi_of->op.get() : nullptr);
+      if (solves) { *solves = st.solves; }
+      if (converged) { *converged = st.converged ? 1 : 0; }
+      if (iterations) { *iterations = st.iterations; }
+   });
 }
 
 void ecm2_operator_destroy(ecm2_operator *op) { delete op; }

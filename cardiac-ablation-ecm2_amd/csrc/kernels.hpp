@@ -2,7 +2,8 @@
 // coefficient setup; k_tpe.hip: thread-per-element p <= 2 apply and diagonal; k_line.hip:
 // line / brick p >= 3 apply and the sum-factorised diagonal; k_misc.hip: workgroup-per-element
 // apply, restriction, vector and solver kernels; k_lform.hip: the linear form's element vectors;
-// k_bdr.hip: the boundary-face terms; k_conv.hip: the convection term).
+// k_bdr.hip: the boundary-face terms; k_conv.hip: the convection term; k_bicgstab.hip: the BiCGSTAB loop's
+// vector passes).
 //
 // Quadrature-data layouts (the qdata a PA form owns):
 //  * BLOCKED (fused thread-per-element kernel): elements in blocks of 64 (one
@@ -668,6 +669,60 @@ void scatter_add_idx(int n, const int *idx, const double *buf, double *y, hipStr
 // s_h = runs[r][8 + h] for h < 4, else rslots[slot_off + h].  runs has a sentinel row.
 void sum_partials(int b0, int b1, const int *blocks, const int *runs, const int *rslots, const int *pdof, const double *part,
                   int n_owned, double *y, double *yg, hipStream_t s);
+
+// ---- vector kernels for the device BiCGSTAB (k_bicgstab.hip) ----
+// BiCGSTABSolver::Mult's iteration (linalg/solvers.cpp:1650-1784) in five vector passes, about 23 vector
+// streams beside its two Mults (one BLAS-1 call per line moves about 30), the same operations per entry
+// in the reference's order.  The loop is driven by the device as the PCG's: its state is BcgCtl (device
+// memory, and a mapped coherent host mirror the host polls), the scalars live in BcgScal, the stopping
+// decisions (bicgstab_stop.hpp) run in bcg_final, and every kernel returns at once when ctl->done is set.
+// No atomics: every partial list is parked one per workgroup and summed in a fixed order.
+struct BcgCtl
+{
+   int done, iters, checked, pad;   // BcgDone; final_iter; (mirror) the last iteration whose tests all ran
+   double final;                    // final_norm
+};
+struct BcgScal
+{
+   double rho1, rho2, alpha, omega;  // rho_1 = (r~, r) of the running iteration, rho_2, alpha, omega of the last
+   double rtv, ts, tt;               // (r~, v), (t, s), (t, t)
+   double resid;                     // ||s|| or ||r||, the last norm tested
+};
+// the partial lists' stride: list k of a pass at partials + k * bcg_parts(n); the buffer holds two lists
+int bcg_parts(int n);
+enum BcgFinalMode : int
+{
+   BCG_FINAL_DOT = 0,   // *out = the sum of list 0 (+ hout, the mapped host scalar); no test
+   BCG_FINAL_DOT2 = 1,  // sc->ts, sc->tt = the sums of lists 0, 1; no test
+   BCG_FINAL_S = 2,     // sc->resid = ||s|| = sqrt(list 0): BCG_TEST_S of iteration `it`
+   BCG_FINAL_R = 3      // sc->resid = ||r|| = sqrt(list 0): BCG_TEST_R, BCG_TEST_OMEGA (sc->omega) of iteration `it`;
+                        // then rho_2 = rho_1, rho_1 = list 1 and BCG_TEST_RHO of iteration it + 1; marks `it` checked
+};
+struct BcgFinal
+{
+   int mode = BCG_FINAL_DOT, it = 0, max_iter = 0;
+   double tol_goal = 0.0;
+   BcgCtl *ctl = nullptr, *host = nullptr;
+   BcgScal *sc = nullptr;
+   double *out = nullptr, *hout = nullptr;
+};
+// lists 0, 1 = the partials of (a, b) and (a, c) in one pass over a, b, c (c null: list 0 alone; c == a reads
+// a once), a flat grid of contiguous chunks; then bcg_final(f)
+void bcg_dot(int n, const double *a, const double *b, const double *c, double *partials, const BcgFinal &f, hipStream_t s);
+// it == 1: p = r; else beta = (rho_1 / rho_2) (alpha / omega), p = r + beta (p - omega v); phat = dinv .* p
+// (dinv null: phat = p)
+void bcg_update_p(int n, int it, const BcgScal *sc, double *p, const double *v, const double *r, const double *dinv,
+                  double *phat, const BcgCtl *ctl, hipStream_t s);
+// alpha = rho_1 / (r~, v) (-> sc->alpha); s = r - alpha v into r's storage; shat = dinv .* s (dinv null: shat
+// is not written, s serves); list 0 = the partials of ||s||^2; then bcg_final(f) (BCG_FINAL_S)
+void bcg_update_s(int n, BcgScal *sc, double *r, const double *v, const double *dinv, double *shat, double *partials,
+                  const BcgFinal &f, hipStream_t s);
+// omega = (t, s) / (t, t) (-> sc->omega); x = (x + alpha phat) + omega shat; r = s - omega t (s in r's storage);
+// lists 0, 1 = the partials of ||r||^2 and (r~, r); then bcg_final(f) (BCG_FINAL_R)
+void bcg_update_xr(int n, BcgScal *sc, double *x, const double *phat, const double *shat, double *r, const double *t,
+                   const double *rt, double *partials, const BcgFinal &f, hipStream_t s);
+// after the loop: x += alpha phat when it stopped at a ||s|| test
+void bcg_finish_x(int n, const BcgScal *sc, const double *phat, double *x, const BcgCtl *ctl, hipStream_t s);
 } // namespace kern
 
 } // namespace ecm2

@@ -1,5 +1,6 @@
 // solvers.cpp -- see solvers.hpp.
 #include "solvers.hpp"
+#include "bicgstab_stop.hpp"
 
 #include <thread>
 
@@ -326,6 +327,199 @@ PCGResult pcg_solve(PAForm &A, const int *ess, int n_ess, const double *b, doubl
 }
 
 // ---------------------------------------------------------------------------------------
+// ConstrainedOperator + BiCGSTABSolver + OperatorJacobiSmoother(second operator)
+// ---------------------------------------------------------------------------------------
+namespace
+{
+// BiCGSTABSolver's work vectors (UpdateVectors, solvers.cpp:1579-1604; s lives in r's storage), as
+// PCGWork: one workspace per host thread and device, grown on demand.
+struct BcgWork
+{
+   DeviceArray<double> r, rt, p, phat, v, shat, t, dinv, saved, partials;
+   DeviceArray<kern::BcgScal> sc;
+   DeviceArray<kern::BcgCtl> ctl;                      // the device-driven loop's state
+   kern::BcgCtl *hctl = nullptr, *hctl_dev = nullptr;  // its mapped pinned mirror (coherent: polled while kernels run)
+   double *hs = nullptr, *hs_dev = nullptr;            // mapped pinned scalar: (r_0, r_0)
+   ~BcgWork()
+   {
+      if (hs) { (void)hipHostFree(hs); }
+      if (hctl) { (void)hipHostFree(hctl); }
+   }
+   void ensure(int n, int n_ess, bool jacobi)
+   {
+      auto grow = [](DeviceArray<double> &a, size_t m) {
+         if (a.size() < m) { a.resize(m); }
+      };
+      const size_t m = std::max(n, 1);
+      for (DeviceArray<double> *a : {&r, &rt, &p, &phat, &v, &t}) { grow(*a, m); }
+      if (jacobi)
+      {
+         grow(shat, m);
+         grow(dinv, m);
+      }
+      grow(saved, std::max(n_ess, 1));
+      grow(partials, 2 * (size_t)kern::bcg_parts(n));
+      if (!hs)
+      {
+         ECM2_HIP(hipHostMalloc(&hs, sizeof(double), hipHostMallocMapped));
+         ECM2_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&hs_dev), hs, 0));
+         ECM2_HIP(hipHostMalloc(&hctl, sizeof(kern::BcgCtl), hipHostMallocMapped | hipHostMallocCoherent));
+         ECM2_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&hctl_dev), hctl, 0));
+         ctl.resize(1);
+         sc.resize(1);
+      }
+   }
+};
+
+BcgWork &bcg_work()
+{
+   static thread_local std::vector<std::unique_ptr<BcgWork>> per_device;
+   int dev = 0;
+   ECM2_HIP(hipGetDevice(&dev));
+   if ((int)per_device.size() <= dev) { per_device.resize(dev + 1); }
+   if (!per_device[dev]) { per_device[dev].reset(new BcgWork()); }
+   return *per_device[dev];
+}
+} // namespace
+
+PCGResult bicgstab_solve(LinOp &A, LinOp *jacobi_of, const int *ess, int n_ess, const double *b, double *x,
+                         double rel_tol, double abs_tol, int max_iter, hipStream_t s)
+{
+   // refused before anything is enqueued: k_bcg_update_xr reads and writes the caller's x two entries at a time
+   ECM2_VERIFY(((uintptr_t)x % 16) == 0, ERR_ARG,
+               "BiCGSTAB: x must be 16-byte aligned (got " << (const void *)x << ")");
+   ECM2_VERIFY(!A.distributed(), ERR_UNSUPPORTED,
+               "BiCGSTAB: distributed operators are not supported (no distributed form carries the convection term)");
+   const int n = A.size();
+   ECM2_VERIFY(!jacobi_of || jacobi_of->size() == n, ERR_ARG,
+               "BiCGSTAB: the preconditioner's operator has size " << jacobi_of->size() << ", the operator " << n);
+   PCGResult res;
+   BcgWork &w = bcg_work();
+   const bool jacobi = jacobi_of != nullptr;
+   w.ensure(n, n_ess, jacobi);
+   double *r = w.r.data(), *rt = w.rt.data(), *p = w.p.data(), *phat = w.phat.data(), *v = w.v.data(), *t = w.t.data();
+   double *dinv = jacobi ? w.dinv.data() : nullptr, *shat = jacobi ? w.shat.data() : nullptr;
+   double *partials = w.partials.data();
+   kern::BcgScal *sc = w.sc.data();
+   kern::BcgCtl *ctl = w.ctl.data(), *hm = w.hctl;
+   // the loop's state, reset first (no kernel of a previous solve writes the mirror any more: every solve
+   // ends synchronised, an ERR_NUMERIC one included)
+   ECM2_HIP(hipMemsetAsync(ctl, 0, sizeof(kern::BcgCtl), s));
+   ECM2_HIP(hipMemsetAsync(sc, 0, sizeof(kern::BcgScal), s));
+   *hm = kern::BcgCtl{};
+   // ConstrainedOperator::ConstrainedMult, DIAG_ONE: pcg_solve's cmult
+   auto cmult = [&](double *in, double *out) {
+      if (n_ess == 0) { A.mult(in, out, s); return; }
+      kern::ess_save_zero(n_ess, ess, in, w.saved.data(), s);
+      A.mult(in, out, s);
+      kern::ess_restore(n_ess, ess, w.saved.data(), in, out, s);
+   };
+   if (jacobi)
+   {
+      // OperatorJacobiSmoother(jacobi_of's diagonal, ess): essential rows get diag 1
+      jacobi_of->diagonal(t, s);
+      if (n_ess) { kern::set_values(n_ess, ess, 1.0, t, s); }
+      kern::reciprocal(n, t, dinv, s);
+   }
+   // x = 0, r = b, r~ = r (solvers.cpp:1623-1628)
+   if (n)
+   {
+      ECM2_HIP(hipMemsetAsync(x, 0, sizeof(double) * n, s));
+      ECM2_HIP(hipMemcpyAsync(r, b, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+      ECM2_HIP(hipMemcpyAsync(rt, b, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+   }
+   // (r~, r) = ||r_0||^2 is also iteration 1's rho_1, summed by the pass that sums (r~, v)
+   kern::BcgFinal fin;
+   fin.ctl = ctl;
+   fin.host = w.hctl_dev;
+   fin.sc = sc;
+   fin.max_iter = max_iter;
+   fin.mode = kern::BCG_FINAL_DOT;
+   fin.out = &sc->rho1;
+   fin.hout = w.hs_dev;
+   kern::bcg_dot(n, rt, r, nullptr, partials, fin, s);
+   ECM2_HIP(hipStreamSynchronize(s));
+   const double nrm0 = *(volatile double *)w.hs;
+   const double resid0 = nrm0 >= 0 ? std::sqrt(nrm0) : nrm0;
+   // the reference's checks before the loop (solvers.cpp:1630-1648)
+   const double tol_goal = std::max(resid0 * rel_tol, abs_tol);
+   const int start = bcg_stop(BCG_TEST_R0, resid0, tol_goal, 0, max_iter);
+   ECM2_VERIFY(start != BCG_NONFINITE, ERR_NUMERIC, "BiCGSTAB: resid = " << resid0);
+   res.initial_norm = res.final_norm = resid0;
+   if (start == BCG_CONVERGED)
+   {
+      res.converged = true;
+      return res;
+   }
+   if (max_iter < 1) { return res; }  // (the loop does not run: not converged, final_norm = ||r_0||)
+   fin.tol_goal = tol_goal;
+   fin.hout = nullptr;
+   auto vol = [](const int &q) { return *(volatile const int *)&q; };
+   // has the loop stopped at an iteration <= waited?  (waits until the tests of `waited` ran; pcg_solve's)
+   auto stopped_by = [&](int waited) {
+      for (long spin = 1;; spin++)
+      {
+         if (vol(hm->checked) >= waited)
+         {
+            // (the device writes done before checked: a stop at `waited` is visible now)
+            // (a rho_1 == 0 stop found in the tail of `waited` carries final_iter = waited + 1)
+            return vol(hm->done) != 0;
+         }
+         if (vol(hm->done) != 0) { return true; }  // (nothing past `waited` is enqueued yet)
+         if (spin % 4096 == 0)
+         {
+            const hipError_t e = hipStreamQuery(s);
+            if (e == hipSuccess && vol(hm->checked) < waited && vol(hm->done) == 0)
+            {
+               ECM2_VERIFY(false, ERR_INTERNAL, "device BiCGSTAB loop: stream idle before the tests of iteration " << waited);
+            }
+            if (e != hipSuccess && e != hipErrorNotReady) { ECM2_HIP(e); }
+         }
+         // back off after a short spin: the host core stays free while the device runs the iteration
+         if (spin > 256) { std::this_thread::yield(); }
+      }
+   };
+   // BiCGSTABSolver's loop (solvers.cpp:1650-1784) driven by the device: the host enqueues iteration i as
+   // soon as the last test of i - 1 has run (it polls the mirror's progress mark; no host synchronisation
+   // of the stream) and ends at the iteration the device stopped at; at most the stopping iteration's
+   // Mults run after the stop.
+   for (int i = 1;; i++)
+   {
+      if (i > 1 && stopped_by(i - 1)) { break; }
+      fin.it = i;
+      // p, phat
+      kern::bcg_update_p(n, i, sc, p, v, r, dinv, phat, ctl, s);
+      // v = A phat, (r~, v)
+      cmult(phat, v);
+      fin.mode = kern::BCG_FINAL_DOT;
+      fin.out = &sc->rtv;
+      kern::bcg_dot(n, rt, v, nullptr, partials, fin, s);
+      // alpha, s, shat, ||s|| and its test
+      fin.mode = kern::BCG_FINAL_S;
+      kern::bcg_update_s(n, sc, r, v, dinv, shat, partials, fin, s);
+      // t = A shat, (t, s) and (t, t)
+      cmult(shat ? shat : r, t);
+      fin.mode = kern::BCG_FINAL_DOT2;
+      kern::bcg_dot(n, t, r, t, partials, fin, s);
+      // omega, x, r, ||r|| and (r~, r) with the tests of ||r||, omega, max_iter and the next rho_1
+      fin.mode = kern::BCG_FINAL_R;
+      kern::bcg_update_xr(n, sc, x, phat, shat, r, t, rt, partials, fin, s);
+      if (i >= max_iter) { break; }
+   }
+   // the stopping iteration's x += alpha phat (a ||s|| stop)
+   kern::bcg_finish_x(n, sc, phat, x, ctl, s);
+   ECM2_HIP(hipStreamSynchronize(s));
+   const int done = vol(hm->done);
+   ECM2_VERIFY(done != BCG_RUNNING, ERR_INTERNAL, "device BiCGSTAB loop ended without a stop");
+   const double fn = hm->final;
+   ECM2_VERIFY(done != BCG_NONFINITE, ERR_NUMERIC, "BiCGSTAB: resid = " << fn << " at iteration " << hm->iters);
+   res.final_norm = fn;
+   res.iterations = hm->iters;
+   res.converged = bcg_converged(done);
+   return res;
+}
+
+// ---------------------------------------------------------------------------------------
 // SDIRK family (slope form, ImplicitVarType::SLOPE) on an ex16-style conduction operator
 // ---------------------------------------------------------------------------------------
 namespace
@@ -363,9 +557,11 @@ double ode_implicit_coeff(int type)
 }
 
 StepStats ode_step(int type, LinOp &T, LinOp &K, double dt, double *u, const int *ess, int n_ess,
-                   double rel_tol, int max_iter, bool jacobi, hipStream_t s, const double *b)
+                   double rel_tol, int max_iter, bool jacobi, hipStream_t s, const double *b, int solver,
+                   LinOp *jacobi_of)
 {
    ECM2_VERIFY(ode_implicit_supported(type), ERR_ARG, "unsupported implicit ODE solver type " << type);
+   ECM2_VERIFY(solver == STAGE_PCG || solver == STAGE_BICGSTAB, ERR_ARG, "unknown stage solver " << solver);
    ECM2_VERIFY(T.size() == K.size(), ERR_ARG, "T and K sizes differ");
    const int n = T.size();
    StepStats st;
@@ -376,7 +572,9 @@ StepStats ode_step(int type, LinOp &T, LinOp &K, double dt, double *u, const int
       kern::scale(n, -1.0, rhs.data(), s);
       if (b) { kern::add_scaled(n, rhs.data(), 1.0, b, rhs.data(), s); }
       if (n_ess) { kern::set_values(n_ess, ess, 0.0, rhs.data(), s); }
-      const PCGResult r = pcg_solve(T, ess, n_ess, rhs.data(), kk, rel_tol, 0.0, max_iter, jacobi, s);
+      const PCGResult r = solver == STAGE_BICGSTAB
+                             ? bicgstab_solve(T, jacobi_of, ess, n_ess, rhs.data(), kk, rel_tol, 0.0, max_iter, s)
+                             : pcg_solve(T, ess, n_ess, rhs.data(), kk, rel_tol, 0.0, max_iter, jacobi, s);
       st.solves++;
       st.iterations += r.iterations;
       st.max_iterations = std::max(st.max_iterations, r.iterations);

@@ -1,4 +1,4 @@
-// solvers.hpp -- the callers of the PA operator: constrained Jacobi-PCG and the SDIRK
+// solvers.hpp -- the callers of the PA operator: constrained Jacobi-PCG, constrained BiCGSTAB and the SDIRK
 // time steppers of an ex16-style conduction (Pennes bioheat) operator, all device
 // resident, over one operator interface that the serial form, the RCCL-distributed form
 // and the in-process loopback group implement.
@@ -7,6 +7,7 @@
 //   Operator (the solver-facing interface)     linalg/operator.hpp:24-110
 //   ConstrainedOperator DIAG_ONE               linalg/operator.cpp:586-646
 //   CGSolver::Mult                             linalg/solvers.cpp:869-1004
+//   BiCGSTABSolver::Mult                       linalg/solvers.cpp:1579-1805
 //   OperatorJacobiSmoother (PA diagonal)       linalg/solvers.hpp:421, bilinearform_ext.cpp:370-454
 //   parallel dot (MPI_Allreduce)               linalg/hypre / InnerProduct(comm, ...)
 //   BackwardEuler / SDIRK23 / SDIRK33 / ImplicitMidpoint / SDIRK34 ::Step
@@ -127,6 +128,20 @@ PCGResult pcg_solve(LinOp &A, const int *ess_dev, int n_ess, const double *b, do
 PCGResult pcg_solve(PAForm &A, const int *ess_dev, int n_ess, const double *b, double *x,
                     double rel_tol, double abs_tol, int max_iter, bool jacobi, hipStream_t s);
 
+// Constrained (DIAG_ONE on ess) BiCGSTAB for a nonsymmetric A (a form with a ConvectionIntegrator), x
+// overwritten (iterative_mode = false): BiCGSTABSolver::Mult (linalg/solvers.cpp:1579-1805) restated
+// around the same constrained Mult as the PCG, the iteration's vector work in the fused passes of
+// k_bicgstab.hip, the loop driven by the device.  final_norm = ||r|| or ||s|| (norms, as the reference's
+// tol_goal = max(||r_0|| rel_tol, abs_tol)); iterations = final_iter.  Not converged: rho_1 == 0, omega == 0,
+// max_iter.  A non-finite ||r_0||, ||s|| or ||r|| (alpha = rho_1 / 0 among them), where MFEM_VERIFY aborts:
+// ERR_NUMERIC.
+// jacobi_of (or null: no preconditioner): OperatorJacobiSmoother built from a second operator of A's size --
+// dinv = 1 / diag(jacobi_of), essential rows 1 -- as a caller builds it from the symmetric part, since the
+// diagonal of a form with an active convection integrator is refused.
+// A distributed operator (distributed() == true): ERR_UNSUPPORTED.  x must be 16-byte aligned (ERR_ARG).
+PCGResult bicgstab_solve(LinOp &A, LinOp *jacobi_of, const int *ess_dev, int n_ess, const double *b, double *x,
+                         double rel_tol, double abs_tol, int max_iter, hipStream_t s);
+
 // ODESolver::SelectImplicit numbering (ode.cpp:77-91): 21 BackwardEuler, 22 SDIRK23(L-stable),
 // 23 SDIRK33, 32 ImplicitMidpoint, 33 SDIRK23 (A-stable, order 3), 34 SDIRK34.
 bool ode_implicit_supported(int type);
@@ -145,7 +160,13 @@ struct StepStats
 // b (optional, device, true dofs in the operator's numbering): a source frozen over the step,
 // M du/dt = -K u + b -- every stage solves T k = -K u_stage + b (essential rows zeroed as before);
 // null: exactly the homogeneous step.
+// solver: the stage solver.  STAGE_PCG (the default: the launches above, `jacobi` its preconditioner switch);
+// STAGE_BICGSTAB: bicgstab_solve with jacobi_of -- the caller assembles T = M + c*dt*(K_sym + C) and
+// K = K_sym + C with the convection inside both, and passes jacobi_of = M + c*dt*K_sym (null: none;
+// `jacobi` is not read).
+enum StageSolver : int { STAGE_PCG = 0, STAGE_BICGSTAB = 1 };
 StepStats ode_step(int type, LinOp &T, LinOp &K, double dt, double *u, const int *ess_dev, int n_ess,
-                   double rel_tol, int max_iter, bool jacobi, hipStream_t s, const double *b = nullptr);
+                   double rel_tol, int max_iter, bool jacobi, hipStream_t s, const double *b = nullptr,
+                   int solver = STAGE_PCG, LinOp *jacobi_of = nullptr);
 
 } // namespace ecm2

@@ -58,6 +58,8 @@ extern "C" {
  *           ecm2_pa_form_assemble_diagonal returns ECM2_ERR_UNSUPPORTED on a form whose convection
  *           integrator has an active element, and so does ecm2_pcg_solve(jacobi = 1) on it.  Put the
  *           convection in the explicit operator K of ecm2_ode_step only: T = M + c dt K_sym stays symmetric.
+ *           Or take it implicitly: ecm2_operator_bicgstab / ecm2_ode_step_bicgstab solve the nonsymmetric
+ *           T = M + c dt (K_sym + C), with the Jacobi preconditioner built from the symmetric part.
  *   ecm2_pa_form_energy_parts is 0 for such a form.  At most one per form (a second: ECM2_ERR_UNSUPPORTED);
  *   distributed forms (ecm2_par_form_add_integrator[_marked]) return ECM2_ERR_UNSUPPORTED. */
 #define ECM2_CONVECTION 2
@@ -461,6 +463,33 @@ int ecm2_ode_step(int type, ecm2_operator *T, ecm2_operator *K, double dt, doubl
 int ecm2_ode_step_source(int type, ecm2_operator *T, ecm2_operator *K, const double *b, double dt, double *u,
                          const int *ess, int n_ess, double rel_tol, int max_iter, int jacobi, int *solves,
                          int *iterations, int *converged, void *stream);
+/* ConstrainedOperator (operator.cpp:586-646) + BiCGSTABSolver::Mult (linalg/solvers.cpp:1579-1805) for a
+ * nonsymmetric operator (a form with a ConvectionIntegrator), iterative_mode = false: x is overwritten
+ * and must be 16-byte aligned (ECM2_ERR_ARG otherwise, before anything is enqueued).
+ * jacobi_of (NULL: no preconditioner): OperatorJacobiSmoother built from a second operator of A's size
+ * (ECM2_ERR_ARG otherwise), dinv = 1 / diag(jacobi_of) with the essential rows 1 -- as an MFEM user builds
+ * it from the symmetric form, since the diagonal of a form with an active convection integrator is refused.
+ * The reference's operations per entry and its stops, on norms: tol_goal = max(||r_0|| rel_tol, abs_tol);
+ * ||r_0|| <= tol_goal converges with 0 iterations; ||s|| < tol_goal converges after x += alpha phat;
+ * ||r|| < tol_goal converges; rho_1 == 0, omega == 0 and max_iter stop not converged
+ * (ecm2_bicgstab_last_converged() == 0).  iterations = final_iter, final_norm = the last ||s|| or ||r||.
+ * A non-finite ||r_0||, ||s|| or ||r|| (alpha = rho_1 / 0 included), where MFEM_VERIFY aborts, returns
+ * ECM2_ERR_NUMERIC.  Serial forms and loopback groups; an operator whose dots need communication (an
+ * RCCL rank, a group member) returns ECM2_ERR_UNSUPPORTED.  Two solves are bitwise equal. */
+int ecm2_operator_bicgstab(ecm2_operator *A, ecm2_operator *jacobi_of /* NULL: none */, const int *ess, int n_ess,
+                           const double *b, double *x, double rel_tol, double abs_tol, int max_iter,
+                           int *iterations, double *final_norm, void *stream);
+/* IterativeSolver::GetConverged() of the calling thread's last ecm2_operator_bicgstab (BiCGSTABSolver,
+ * linalg/solvers.cpp:1579-1805): 1 converged, 0 not (or no solve yet); per calling thread, as
+ * ecm2_pcg_last_converged. */
+int ecm2_bicgstab_last_converged(void);
+/* ecm2_ode_step_source with the advection implicit: the stage solves run BiCGSTABSolver (linalg/solvers.cpp:
+ * 1579-1805) instead of the PCG.  The caller assembles T = M + c*dt*(K_sym + C) and K = K_sym + C (the
+ * ConvectionIntegrator inside both) and passes jacobi_of = M + c*dt*K_sym (NULL: no preconditioner); every
+ * stage solves T k = -K u_stage [+ b] with the essential rows zeroed.  b == NULL: no source. */
+int ecm2_ode_step_bicgstab(int type, ecm2_operator *T, ecm2_operator *jacobi_of, ecm2_operator *K, const double *b /* NULL */,
+                           double dt, double *u, const int *ess, int n_ess, double rel_tol, int max_iter,
+                           int *solves, int *iterations, int *converged, void *stream);
 void ecm2_operator_destroy(ecm2_operator *op);
 
 /* ------------------------------------------------------------------------ */
