@@ -1,5 +1,5 @@
 // dev_common.hpp -- device-side helpers shared by the gfx950 kernel translation units
-// (k_setup.hip, k_tpe.hip, k_line.hip, k_misc.hip, k_lform.hip, k_bdr.hip, k_conv.hip).  Included by .hip files only.
+// (k_setup.hip, k_tpe.hip, k_line.hip, k_misc.hip, k_lform.hip, k_bdr.hip, k_conv.hip, k_bicgstab.hip).  Included by .hip files only.
 #pragma once
 
 #include "kernels.hpp"
@@ -155,6 +155,68 @@ __device__ __forceinline__ CBasis *stage_basis(const Basis1D *tab)
    CBasis *p = (CBasis *)tab;
    asm volatile("" : "+s"(p));
    return p;
+}
+
+// ---- deterministic sums and the device-driven solver loops (k_misc.hip: PCG, k_bicgstab.hip: BiCGSTAB) ----
+// Pass 1 of a deterministic sum: one partial per workgroup of 256, partials[blockIdx.x] (a fixed order within
+// the workgroup); `red`: 4 doubles of LDS.
+__device__ __forceinline__ void park_partial(double s, double *__restrict__ partials, double *red)
+{
+   for (int off = 32; off > 0; off >>= 1) { s += __shfl_down(s, off, 64); }
+   if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s; }
+   __syncthreads();
+   if (threadIdx.x == 0) { partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]); }
+}
+
+// Pass 2 (one workgroup of kFinalThreads): every thread calls it; thread 0 returns the sum of the partials in
+// a fixed order -- eight running sums per thread (eight loads in flight, for long partial lists: one partial
+// per brick (78,608 at C5) took 77 dependent loads per thread), their pairwise sum, the wave's shuffle tree,
+// the waves' sums in pairs.  `red`: kFinalThreads / 64 doubles of LDS.  (1,024 threads: the 4,921 energy
+// partials of a C4 Mult are 5 loads per thread, not 20 -- a latency-bound single workgroup, 8.5 -> ~4 us per
+// PCG iteration, profiles/r6/gpu3.)
+constexpr int kFinalThreads = 1024;
+__device__ __forceinline__ double sum_partials_fixed(int nparts, const double *__restrict__ partials, double *red)
+{
+   constexpr int NW = kFinalThreads / 64, U = 8;
+   double a[U] = {};
+   int i = threadIdx.x;
+   for (; i + (U - 1) * kFinalThreads < nparts; i += U * kFinalThreads)
+   {
+#pragma unroll
+      for (int u = 0; u < U; u++) { a[u] += partials[i + u * kFinalThreads]; }
+   }
+   for (; i < nparts; i += kFinalThreads) { a[0] += partials[i]; }
+   double s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+   for (int off = 32; off > 0; off >>= 1) { s += __shfl_down(s, off, 64); }
+   if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s; }
+   __syncthreads();
+   double v = 0.0;
+   if (threadIdx.x == 0)
+   {
+#pragma unroll
+      for (int k = 0; k < NW; k += 2) { v += red[k] + red[k + 1]; }
+   }
+   return v;
+}
+
+// A loop's stop (kernels.hpp LoopCtl), written once by the one thread that found it: the device state, then
+// the mirror's fields before its flag.
+__device__ __forceinline__ void loop_set_done(kern::LoopCtl *ctl, kern::LoopCtl *host, int done, int iters, double final)
+{
+   ctl->done = done;
+   ctl->iters = iters;
+   ctl->final = final;
+   host->final = final;
+   host->iters = iters;
+   __threadfence_system();  // (the mirror's fields before its flag)
+   host->done = done;
+}
+
+// Iteration `it`'s tests have all run: the progress mark the host polls, after the flag.
+__device__ __forceinline__ void loop_mark_checked(kern::LoopCtl *host, int it)
+{
+   __threadfence_system();  // (the flag before the mark)
+   host->checked = it;
 }
 
 } // namespace dev

@@ -6,9 +6,9 @@
 //   bcg_dot        2           (t, s) and (t, t) in one pass
 //   bcg_update_xr  8           x = (x + alpha phat) + omega shat, r = s - omega t, ||r||^2, (r~, r)
 // -- 23 vector streams an iteration.  Each pass that reduces parks one partial per workgroup in a fixed
-// order and a one-workgroup final pass sums them in a fixed order (no atomics: two solves are bitwise
-// equal) and runs the reference's stopping decision (bicgstab_stop.hpp) on the device; once one stops,
-// every later kernel of the solve returns at once (kernels.hpp, BcgCtl).
+// order (dev_common.hpp park_partial) and a one-workgroup final pass sums them in a fixed order (no atomics:
+// two solves are bitwise equal) and runs the reference's stopping decision (bicgstab_stop.hpp) on the device;
+// once one stops, every later kernel of the solve returns at once (kernels.hpp, LoopCtl).
 #include "dev_common.hpp"
 #include "bicgstab_stop.hpp"
 
@@ -19,18 +19,9 @@ namespace ecm2
 namespace
 {
 using namespace dev;
-using kern::BcgCtl;
+using kern::LoopCtl;
 using kern::BcgScal;
 using kern::BcgFinal;
-
-// one partial per workgroup of 256 (a fixed order within the workgroup); `red`: 4 doubles of LDS
-__device__ __forceinline__ void bcg_park(double s, double *__restrict__ partials, double *red)
-{
-   for (int off = 32; off > 0; off >>= 1) { s += __shfl_down(s, off, 64); }
-   if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s; }
-   __syncthreads();
-   if (threadIdx.x == 0) { partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]); }
-}
 
 // The read-only reductions take k_dot_partial's flat grid of contiguous chunks (workgroup b sums pairs
 // [b kChunk, (b + 1) kChunk)); the passes that write vectors and park partials take k_pcg_step_r's
@@ -40,7 +31,7 @@ constexpr int kK = 4, kChunk = 256 * kK, kBlocks = 1024;
 // lists 0 and 1 (stride np): the partials of (a, b) and, with c, of (a, c); c == a: a read once
 __global__ void __launch_bounds__(256)
 k_bcg_dot(int n, const double *__restrict__ a, const double *__restrict__ b, const double *c, int np,
-          double *__restrict__ partials, const BcgCtl *ctl)
+          double *__restrict__ partials, const LoopCtl *ctl)
 {
    if (ctl->done) { return; }  // (wave-uniform)
    __shared__ double red[8];
@@ -71,8 +62,8 @@ k_bcg_dot(int n, const double *__restrict__ a, const double *__restrict__ b, con
       s0 += a[n - 1] * b[n - 1];
       if (c) { s1 += a[n - 1] * c[n - 1]; }
    }
-   bcg_park(s0, partials, red);
-   if (c) { bcg_park(s1, partials + np, red + 4); }
+   park_partial(s0, partials, red);
+   if (c) { park_partial(s1, partials + np, red + 4); }
 }
 
 // The direction (solvers.cpp:1676-1693): it == 1 copies r; else beta = (rho_1 / rho_2) (alpha / omega),
@@ -80,7 +71,7 @@ k_bcg_dot(int n, const double *__restrict__ a, const double *__restrict__ b, con
 __global__ void __launch_bounds__(256)
 k_bcg_update_p(int n, int it, const BcgScal *__restrict__ sc, double *__restrict__ p, const double *__restrict__ v,
                const double *__restrict__ r, const double *__restrict__ dinv, double *__restrict__ phat,
-               const BcgCtl *ctl)
+               const LoopCtl *ctl)
 {
    // entries 2i, 2i + 1 per lane (the last lane of an odd n takes the tail)
    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x, n2 = n / 2;
@@ -122,7 +113,7 @@ k_bcg_update_p(int n, int it, const BcgScal *__restrict__ sc, double *__restrict
 __global__ void __launch_bounds__(256)
 k_bcg_update_s(int n, BcgScal *sc, double *__restrict__ r, const double *__restrict__ v,
                const double *__restrict__ dinv, double *__restrict__ shat, double *__restrict__ partials,
-               const BcgCtl *ctl)
+               const LoopCtl *ctl)
 {
    if (ctl->done) { return; }
    __shared__ double red[4];
@@ -147,7 +138,7 @@ k_bcg_update_s(int n, BcgScal *sc, double *__restrict__ r, const double *__restr
       if (dinv) { shat[i] = dinv[i] * sn; }
       s += sn * sn;
    }
-   bcg_park(s, partials, red);
+   park_partial(s, partials, red);
    // (every thread has read rho1 and rtv; nothing in this kernel reads alpha)
    if (blockIdx.x == 0 && threadIdx.x == 0) { sc->alpha = alpha; }
 }
@@ -158,7 +149,7 @@ k_bcg_update_s(int n, BcgScal *sc, double *__restrict__ r, const double *__restr
 __global__ void __launch_bounds__(256)
 k_bcg_update_xr(int n, BcgScal *sc, double *__restrict__ x, const double *__restrict__ phat, const double *shat,
                 double *r, const double *__restrict__ tv, const double *__restrict__ rt, int np,
-                double *__restrict__ partials, const BcgCtl *ctl)
+                double *__restrict__ partials, const LoopCtl *ctl)
 {
    if (ctl->done) { return; }
    __shared__ double red[8];
@@ -194,61 +185,21 @@ k_bcg_update_xr(int n, BcgScal *sc, double *__restrict__ x, const double *__rest
       s0 += rn * rn;
       s1 += rt[i] * rn;
    }
-   bcg_park(s0, partials, red);
-   bcg_park(s1, partials + np, red + 4);
+   park_partial(s0, partials, red);
+   park_partial(s1, partials + np, red + 4);
    if (blockIdx.x == 0 && threadIdx.x == 0) { sc->omega = omega; }
 }
 
 // After the loop: x += alpha phat when it stopped at a ||s|| test (solvers.cpp:1699-1701).
 __global__ void k_bcg_finish_x(int n, const BcgScal *__restrict__ sc, const double *__restrict__ phat,
-                               double *__restrict__ x, const BcgCtl *ctl)
+                               double *__restrict__ x, const LoopCtl *ctl)
 {
    const int i = blockIdx.x * blockDim.x + threadIdx.x;
    if (i >= n || ctl->done != BCG_CONVERGED_S) { return; }
    x[i] = x[i] + sc->alpha * phat[i];
 }
 
-// ---- the final pass: one workgroup sums 1-2 partial lists in a fixed order and decides ----
-constexpr int kFinalThreads = 1024;
-
-// every thread calls it; thread 0 returns the sum (the order of k_dot_final: eight running sums per
-// thread, their pairwise sum, the wave's shuffle tree, the waves' sums in pairs)
-__device__ double bcg_sum(int nparts, const double *__restrict__ partials, double *red)
-{
-   constexpr int NW = kFinalThreads / 64, U = 8;
-   double a[U] = {};
-   int i = threadIdx.x;
-   for (; i + (U - 1) * kFinalThreads < nparts; i += U * kFinalThreads)
-   {
-#pragma unroll
-      for (int u = 0; u < U; u++) { a[u] += partials[i + u * kFinalThreads]; }
-   }
-   for (; i < nparts; i += kFinalThreads) { a[0] += partials[i]; }
-   double s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-   for (int off = 32; off > 0; off >>= 1) { s += __shfl_down(s, off, 64); }
-   if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s; }
-   __syncthreads();
-   double v = 0.0;
-   if (threadIdx.x == 0)
-   {
-#pragma unroll
-      for (int k = 0; k < NW; k += 2) { v += red[k] + red[k + 1]; }
-   }
-   return v;
-}
-
-// the stop, written once: the device state, then the mirror's fields before its flag
-__device__ void bcg_set_done(const BcgFinal &f, int done, int iters, double fin)
-{
-   f.ctl->done = done;
-   f.ctl->iters = iters;
-   f.ctl->final = fin;
-   f.host->final = fin;
-   f.host->iters = iters;
-   __threadfence_system();
-   f.host->done = done;
-}
-
+// ---- the final pass: one workgroup sums 1-2 partial lists in a fixed order (sum_partials_fixed) and decides ----
 __global__ void __launch_bounds__(kFinalThreads)
 k_bcg_final(int nparts, int np, const double *__restrict__ partials, BcgFinal f)
 {
@@ -256,8 +207,8 @@ k_bcg_final(int nparts, int np, const double *__restrict__ partials, BcgFinal f)
    constexpr int NW = kFinalThreads / 64;
    __shared__ double red[2 * NW];
    const bool two = f.mode == kern::BCG_FINAL_DOT2 || f.mode == kern::BCG_FINAL_R;
-   const double v0 = bcg_sum(nparts, partials, red);
-   const double v1 = two ? bcg_sum(nparts, partials + np, red + NW) : 0.0;
+   const double v0 = sum_partials_fixed(nparts, partials, red);
+   const double v1 = two ? sum_partials_fixed(nparts, partials + np, red + NW) : 0.0;
    if (threadIdx.x != 0) { return; }
    BcgScal *sc = f.sc;
    if (f.mode == kern::BCG_FINAL_DOT)
@@ -275,7 +226,7 @@ k_bcg_final(int nparts, int np, const double *__restrict__ partials, BcgFinal f)
       const double resid = sqrt(v0);
       sc->resid = resid;
       const int done = bcg_stop(BCG_TEST_S, resid, f.tol_goal, f.it, f.max_iter);
-      if (done) { bcg_set_done(f, done, f.it, resid); }
+      if (done) { loop_set_done(f.ctl, f.host, done, f.it, resid); }
    }
    else
    {
@@ -293,9 +244,8 @@ k_bcg_final(int nparts, int np, const double *__restrict__ partials, BcgFinal f)
          done = bcg_stop(BCG_TEST_RHO, v1, f.tol_goal, f.it + 1, f.max_iter);
          iters = f.it + 1;
       }
-      if (done) { bcg_set_done(f, done, iters, resid); }
-      __threadfence_system();  // (the flag before the progress mark the host polls)
-      f.host->checked = f.it;
+      if (done) { loop_set_done(f.ctl, f.host, done, iters, resid); }
+      loop_mark_checked(f.host, f.it);
    }
 }
 
@@ -321,7 +271,7 @@ void bcg_dot(int n, const double *a, const double *b, const double *c, double *p
 }
 
 void bcg_update_p(int n, int it, const BcgScal *sc, double *p, const double *v, const double *r, const double *dinv,
-                  double *phat, const BcgCtl *ctl, hipStream_t s)
+                  double *phat, const LoopCtl *ctl, hipStream_t s)
 {
    if (n == 0) { return; }
    hipLaunchKernelGGL(k_bcg_update_p, dim3(grid_for(n / 2 + 1, 256)), dim3(256), 0, s, n, it, sc, p, v, r, dinv, phat,
@@ -346,7 +296,7 @@ void bcg_update_xr(int n, BcgScal *sc, double *x, const double *phat, const doub
    bcg_final(kBlocks, n, partials, f, s);
 }
 
-void bcg_finish_x(int n, const BcgScal *sc, const double *phat, double *x, const BcgCtl *ctl, hipStream_t s)
+void bcg_finish_x(int n, const BcgScal *sc, const double *phat, double *x, const LoopCtl *ctl, hipStream_t s)
 {
    if (n == 0) { return; }
    hipLaunchKernelGGL(k_bcg_finish_x, dim3(grid_for(n, 256)), dim3(256), 0, s, n, sc, phat, x, ctl);

@@ -11,7 +11,8 @@ namespace ecm2
 namespace
 {
 using namespace dev;
-using kern::PcgCtl;
+using kern::LoopCtl;
+using kern::PcgStop;
 using kern::PCG_RUNNING;
 using kern::PCG_CONVERGED;
 using kern::PCG_MAX_ITER;
@@ -255,16 +256,7 @@ __global__ void k_copy_values(int n, const int *__restrict__ idx, const double *
 // positive definite, :955-964); <= r0 -> converged (:972-977); it + 1 > max_iter -> stopped (:979-982).
 // kind 1: the test of den = (A d, d) in iteration it's tail, after ++i (`it` is then the next
 // iteration's number, :993-1004): not finite -> abort; == 0 -> stopped, not converged, final_iter = it.
-struct PcgCheck
-{
-   double r0;
-   int it, max_iter;
-   PcgCtl *ctl, *host;
-   const double *betanom;
-   int kind;
-};
-
-__device__ void pcg_check_one(double v, const PcgCheck &c)
+__device__ void pcg_check_one(double v, const PcgStop &c)
 {
    if (c.ctl->done) { return; }
    int done;
@@ -281,36 +273,14 @@ __device__ void pcg_check_one(double v, const PcgCheck &c)
       done = !isfinite(v) ? PCG_NONFINITE : (v == 0.0 ? PCG_DEN_ZERO : PCG_RUNNING);
       fin = *c.betanom;  // (final_norm = sqrt(betanom) of the iteration, :1047)
    }
-   if (done)
-   {
-      c.ctl->done = done;
-      c.ctl->iters = c.it;
-      c.ctl->final = fin;
-      c.host->final = fin;
-      c.host->iters = c.it;
-      __threadfence_system();  // (the mirror's fields before its flag)
-      c.host->done = done;
-   }
-   if (c.kind == 0)
-   {
-      __threadfence_system();  // (the flag before the progress mark the host polls)
-      c.host->checked = c.it;
-   }
+   if (done) { loop_set_done(c.ctl, c.host, done, c.it, fin); }
+   if (c.kind == 0) { loop_mark_checked(c.host, c.it); }
 }
 
-// Deterministic dot, pass 1: each workgroup writes its sum (a fixed order per workgroup).  (A
+// Deterministic dot, pass 1: each workgroup writes its sum (park_partial: a fixed order per workgroup).  (A
 // one-pass form -- the last workgroup to arrive on a counter sums the parks -- was measured slower:
 // the 1,024 arrivals on one counter serialise, 16.6 vs 6.5 us per dot at a rank's 1.28M dofs,
 // profiles/r5/dot_probe.txt.)
-__device__ __forceinline__ void dot_park(double s, double *__restrict__ partials)
-{
-   __shared__ double red[4];
-   for (int off = 32; off > 0; off >>= 1) { s += __shfl_down(s, off, 64); }
-   if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s; }
-   __syncthreads();
-   if (threadIdx.x == 0) { partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]); }
-}
-
 // (ctl: read only when no check writes it in the same kernel -- no __restrict__ on it)
 // A flat grid of contiguous chunks: workgroup b sums pairs [b kStepChunk, (b + 1) kStepChunk) -- grid-stride
 // loops stream 15-35% slower on this chip (profiles/r6/copy_probe.json: a 16-byte copy 6.67 TB/s flat against
@@ -318,9 +288,10 @@ __device__ __forceinline__ void dot_park(double s, double *__restrict__ partials
 constexpr int kStepK = 4, kStepChunk = 256 * kStepK;
 __global__ void __launch_bounds__(256)
 k_dot_partial(int n, const double *__restrict__ a, const double *__restrict__ b, double *__restrict__ partials,
-              const PcgCtl *ctl)
+              const LoopCtl *ctl)
 {
    if (ctl && ctl->done) { return; }  // (wave-uniform)
+   __shared__ double red[4];
    double s = 0.0;
    const long n2 = n / 2, base = (long)blockIdx.x * kStepChunk + threadIdx.x;
    const v2d *a2 = reinterpret_cast<const v2d *>(a), *b2 = reinterpret_cast<const v2d *>(b);
@@ -336,43 +307,22 @@ k_dot_partial(int n, const double *__restrict__ a, const double *__restrict__ b,
       }
    }
    if ((n & 1) && blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) { s += a[n - 1] * b[n - 1]; }
-   dot_park(s, partials);
+   park_partial(s, partials, red);
 }
 
-// pass 2 (one workgroup of kFinalThreads): the partials in a fixed order; optionally a stopping test on
-// the result.  (1,024 threads: the 4,921 energy partials of a C4 Mult are 5 loads per thread, not 20 --
-// a latency-bound single workgroup, 8.5 -> ~4 us per PCG iteration, profiles/r6/gpu3.)
-constexpr int kFinalThreads = 1024;
+// pass 2 (one workgroup of kFinalThreads, sum_partials_fixed): the partials in a fixed order; with stop.ctl, a
+// stopping test on the result.
 __global__ void __launch_bounds__(kFinalThreads)
 k_dot_final(int nparts, const double *__restrict__ partials, double *__restrict__ out, double *__restrict__ hout,
-            const PcgCtl *ctl, PcgCheck chk, int with_check)
+            const LoopCtl *ctl, PcgStop stop)
 {
    if (ctl && ctl->done) { return; }
-   constexpr int NW = kFinalThreads / 64, U = 8;
-   __shared__ double red[NW];
-   // eight loads in flight per thread (a fixed order: eight running sums, then their pairwise sum), for
-   // long partial lists: one partial per brick (78,608 at C5) took 77 dependent loads per thread
-   double a[U] = {};
-   int i = threadIdx.x;
-   for (; i + (U - 1) * kFinalThreads < nparts; i += U * kFinalThreads)
-   {
-#pragma unroll
-      for (int u = 0; u < U; u++) { a[u] += partials[i + u * kFinalThreads]; }
-   }
-   for (; i < nparts; i += kFinalThreads) { a[0] += partials[i]; }
-   double s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-   for (int off = 32; off > 0; off >>= 1) { s += __shfl_down(s, off, 64); }
-   if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s; }
-   __syncthreads();
-   if (threadIdx.x == 0)
-   {
-      double v = 0.0;
-#pragma unroll
-      for (int k = 0; k < NW; k += 2) { v += red[k] + red[k + 1]; }
-      *out = v;
-      if (hout) { *hout = v; }  // mapped pinned host mirror (the solver's read-back)
-      if (with_check) { pcg_check_one(v, chk); }
-   }
+   __shared__ double red[kFinalThreads / 64];
+   const double v = sum_partials_fixed(nparts, partials, red);
+   if (threadIdx.x != 0) { return; }
+   *out = v;
+   if (hout) { *hout = v; }  // mapped pinned host mirror (the solver's read-back)
+   if (stop.ctl) { pcg_check_one(v, stop); }
 }
 
 // The residual half of CGSolver's update (solvers.cpp:930-947): alpha = nom/den; r -= alpha A d;
@@ -388,9 +338,10 @@ constexpr int kStepBlocks = 1024;
 __global__ void __launch_bounds__(256)
 k_pcg_step_r(int n, const double *__restrict__ nom, const double *__restrict__ den, const double *__restrict__ z,
              double *__restrict__ r, const double *__restrict__ dinv, double *__restrict__ partials,
-             double *__restrict__ alpha_out, const PcgCtl *ctl)
+             double *__restrict__ alpha_out, const LoopCtl *ctl)
 {
    if (ctl && ctl->done) { return; }
+   __shared__ double red[4];
    const double alpha = *nom / *den;
    if (blockIdx.x == 0 && threadIdx.x == 0) { *alpha_out = alpha; }
    double s = 0.0;
@@ -420,7 +371,7 @@ k_pcg_step_r(int n, const double *__restrict__ nom, const double *__restrict__ d
       r[i] = rn;
       s += dinv ? rn * (dinv[i] * rn) : rn * rn;
    }
-   dot_park(s, partials);
+   park_partial(s, partials, red);
 }
 
 // The direction half (solvers.cpp:930, 985-990): x += alpha d (this iteration's alpha = nom/den,
@@ -430,7 +381,7 @@ k_pcg_step_r(int n, const double *__restrict__ nom, const double *__restrict__ d
 __global__ void __launch_bounds__(256)
 k_pcg_update_xd(int n, const double *__restrict__ nom, const double *__restrict__ den,
                 const double *__restrict__ betanom, double *__restrict__ x, double *__restrict__ d,
-                const double *__restrict__ r, const double *__restrict__ dinv, const PcgCtl *ctl)
+                const double *__restrict__ r, const double *__restrict__ dinv, const LoopCtl *ctl)
 {
    // 16-byte accesses: entries 2i, 2i + 1 per lane (the last lane of an odd n takes the tail)
    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x, n2 = n / 2;
@@ -459,7 +410,7 @@ k_pcg_update_xd(int n, const double *__restrict__ nom, const double *__restrict_
 // (converged, max_iter, (B r, r) < 0: CGSolver has already added alpha d then); a den == 0 stop
 // comes after k_pcg_update_xd has run (x complete).
 __global__ void k_pcg_finish_x(int n, const double *__restrict__ alpha, const double *__restrict__ d,
-                               double *__restrict__ x, const PcgCtl *ctl)
+                               double *__restrict__ x, const LoopCtl *ctl)
 {
    const int i = blockIdx.x * blockDim.x + threadIdx.x;
    const int done = ctl->done;
@@ -481,6 +432,7 @@ __global__ void __launch_bounds__(256)
 k_ess_restore(int n, const int *__restrict__ idx, const double *__restrict__ saved, double *__restrict__ v,
               double *__restrict__ y, double *__restrict__ sq_parts)
 {
+   __shared__ double red[4];
    const int i = blockIdx.x * blockDim.x + threadIdx.x;
    double sq = 0.0;
    if (i < n)
@@ -490,7 +442,7 @@ k_ess_restore(int n, const int *__restrict__ idx, const double *__restrict__ sav
       y[idx[i]] = sv;
       sq = sv * sv;
    }
-   if (sq_parts) { dot_park(sq, sq_parts); }
+   if (sq_parts) { park_partial(sq, sq_parts, red); }
 }
 
 __global__ void k_pcg_precond(int n, const double *__restrict__ dinv, const double *__restrict__ r,
@@ -501,7 +453,7 @@ __global__ void k_pcg_precond(int n, const double *__restrict__ dinv, const doub
 }
 
 // one thread: a stopping test after a distributed dot's all-reduce
-__global__ void k_pcg_check(const double *__restrict__ v, PcgCheck chk) { pcg_check_one(*v, chk); }
+__global__ void k_pcg_check(const double *__restrict__ v, PcgStop stop) { pcg_check_one(*v, stop); }
 
 __global__ void k_scale(int n, double a, double *__restrict__ y)
 {
@@ -713,34 +665,23 @@ void copy_values(int n, const int *idx, const double *x, double *y, hipStream_t 
 
 int step_parts(int n) { return std::max(1, (int)((n / 2 + kStepChunk - 1) / kStepChunk)); }
 
-static PcgCheck to_check(const PcgStop *stop)
-{
-   return stop ? PcgCheck{stop->r0, stop->it, stop->max_iter, stop->ctl, stop->host, stop->betanom, stop->kind}
-               : PcgCheck{};
-}
-
 void dot(int n, const double *a, const double *b, double *partials, double *out, hipStream_t s, double *hout,
-         const PcgCtl *ctl, const PcgStop *stop)
+         const LoopCtl *ctl, const PcgStop *stop)
 {
    const int nb = step_parts(n);
    hipLaunchKernelGGL(k_dot_partial, dim3(nb), dim3(256), 0, s, n, a, b, partials, ctl);
-   hipLaunchKernelGGL(k_dot_final, dim3(1), dim3(kFinalThreads), 0, s, nb, partials, out, hout, ctl, to_check(stop),
-                      stop ? 1 : 0);
-   ECM2_HIP(hipGetLastError());
+   dot_final(nb, partials, out, s, ctl, stop, hout);
 }
 
 void pcg_step_r(int n, const double *nom, const double *den, const double *z, double *r, const double *dinv,
-                double *partials, double *out, double *alpha, hipStream_t s, const PcgCtl *ctl, const PcgStop *stop)
+                double *partials, double *out, double *alpha, hipStream_t s, const LoopCtl *ctl, const PcgStop *stop)
 {
-   const int nb = kStepBlocks;
-   hipLaunchKernelGGL(k_pcg_step_r, dim3(nb), dim3(256), 0, s, n, nom, den, z, r, dinv, partials, alpha, ctl);
-   hipLaunchKernelGGL(k_dot_final, dim3(1), dim3(kFinalThreads), 0, s, nb, partials, out, nullptr, ctl, to_check(stop),
-                      stop ? 1 : 0);
-   ECM2_HIP(hipGetLastError());
+   hipLaunchKernelGGL(k_pcg_step_r, dim3(kStepBlocks), dim3(256), 0, s, n, nom, den, z, r, dinv, partials, alpha, ctl);
+   dot_final(kStepBlocks, partials, out, s, ctl, stop);
 }
 
 void pcg_update_xd(int n, const double *nom, const double *den, const double *betanom, double *x, double *d,
-                   const double *r, const double *dinv, hipStream_t s, const PcgCtl *ctl)
+                   const double *r, const double *dinv, hipStream_t s, const LoopCtl *ctl)
 {
    if (n == 0) { return; }
    hipLaunchKernelGGL(k_pcg_update_xd, dim3(grid_for(n / 2 + 1, 256)), dim3(256), 0, s, n, nom, den, betanom, x, d,
@@ -748,7 +689,7 @@ void pcg_update_xd(int n, const double *nom, const double *den, const double *be
    ECM2_HIP(hipGetLastError());
 }
 
-void pcg_finish_x(int n, const double *alpha, const double *d, double *x, hipStream_t s, const PcgCtl *ctl)
+void pcg_finish_x(int n, const double *alpha, const double *d, double *x, hipStream_t s, const LoopCtl *ctl)
 {
    if (n == 0) { return; }
    hipLaunchKernelGGL(k_pcg_finish_x, dim3(grid_for(n, 256)), dim3(256), 0, s, n, alpha, d, x, ctl);
@@ -757,7 +698,7 @@ void pcg_finish_x(int n, const double *alpha, const double *d, double *x, hipStr
 
 void pcg_check(const double *v, const PcgStop &stop, hipStream_t s)
 {
-   hipLaunchKernelGGL(k_pcg_check, dim3(1), dim3(1), 0, s, v, to_check(&stop));
+   hipLaunchKernelGGL(k_pcg_check, dim3(1), dim3(1), 0, s, v, stop);
    ECM2_HIP(hipGetLastError());
 }
 
@@ -777,11 +718,11 @@ void ess_restore(int n, const int *idx, const double *saved, double *v, double *
 
 int ess_parts(int n) { return n > 0 ? grid_for(n, 256) : 0; }
 
-void dot_final(int nparts, const double *partials, double *out, hipStream_t s, const PcgCtl *ctl,
+void dot_final(int nparts, const double *partials, double *out, hipStream_t s, const LoopCtl *ctl,
                const PcgStop *stop, double *hout)
 {
-   hipLaunchKernelGGL(k_dot_final, dim3(1), dim3(kFinalThreads), 0, s, nparts, partials, out, hout, ctl, to_check(stop),
-                      stop ? 1 : 0);
+   hipLaunchKernelGGL(k_dot_final, dim3(1), dim3(kFinalThreads), 0, s, nparts, partials, out, hout, ctl,
+                      stop ? *stop : PcgStop{});
    ECM2_HIP(hipGetLastError());
 }
 

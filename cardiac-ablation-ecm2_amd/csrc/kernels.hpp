@@ -584,12 +584,15 @@ void diagonal(const int *pos, int D, int Q, int layout, int ne, const int *gmap_
 // ---- vector kernels for the device PCG ----
 void set_values(int n, const int *idx, double val, double *y, hipStream_t s);     // y[idx] = val
 void copy_values(int n, const int *idx, const double *x, double *y, hipStream_t s); // y[idx] = x[idx]
-// The device-driven PCG loop's state (device memory; the check kernels also write it to a mapped
-// pinned host mirror): done = PCG_RUNNING or the stop code below; iters, final = the iteration
-// (CGSolver's final_iter) and (B r, r) at which it stopped; checked (mirror) = the last iteration whose
-// betanom test ran.  The vector kernels of an iteration given `ctl` return at once when done is set,
-// so the host can enqueue an iteration before it has read the previous one's test.
-struct PcgCtl
+// The state of a device-driven solver loop, the PCG's and the BiCGSTAB's (device memory; the kernels that
+// run the stopping tests also write it to a mapped pinned host mirror, dev_common.hpp loop_set_done /
+// loop_mark_checked): done = 0 (running) or the method's stop code (PcgDone, BcgDone); iters, final = the
+// iteration (the reference's final_iter) and the value (PCG: (B r, r); BiCGSTAB: final_norm) at which it
+// stopped; checked (mirror) = the progress mark the host polls, the last iteration whose tests ran (BiCGSTAB:
+// all of them; PCG: the betanom test -- the (A d, d) test of the iteration's tail runs after the mark).  The
+// vector kernels of an iteration given `ctl` return at once when done is set, so the host can enqueue an
+// iteration before it has read the previous one's tests.
+struct LoopCtl
 {
    int done, iters, checked, pad;
    double final;
@@ -609,12 +612,13 @@ enum PcgDone
 // A stopping test on the device.  kind 0: iteration `it`'s test of betanom = the dot (non-finite,
 // < 0, <= r0, it + 1 > max_iter); kind 1: the test of den = the dot in iteration it - 1's tail (it =
 // the incremented iteration number, CGSolver's final_iter on a den == 0 stop; final = *betanom).
-// Writes ctl and the host mirror once, when done is first set.
+// Writes ctl and the host mirror once, when done is first set.  Passed to the kernels by value; ctl null:
+// no test.
 struct PcgStop
 {
-   double r0;
-   int it, max_iter;
-   PcgCtl *ctl, *host;
+   double r0 = 0.0;
+   int it = 0, max_iter = 0;
+   LoopCtl *ctl = nullptr, *host = nullptr;
    const double *betanom = nullptr;
    int kind = 0;
 };
@@ -623,7 +627,7 @@ struct PcgStop
 // stop (serial solver): a stopping test on *out in the same launch.
 constexpr int kDotPartials = 1024;
 void dot(int n, const double *a, const double *b, double *partials, double *out, hipStream_t s,
-         double *hout = nullptr, const PcgCtl *ctl = nullptr, const PcgStop *stop = nullptr);
+         double *hout = nullptr, const LoopCtl *ctl = nullptr, const PcgStop *stop = nullptr);
 // CGSolver's update in two passes (4 + 6 vector streams, z never stored):
 //   pcg_step_r: alpha = nom/den (-> *alpha); r -= alpha z (z holds A d); *out = r.(dinv .* r)
 //               (r.r without dinv), deterministic; stop (serial): betanom test in the same launch;
@@ -633,11 +637,11 @@ void dot(int n, const double *a, const double *b, double *partials, double *out,
 // the partials buffer must hold them
 int step_parts(int n);
 void pcg_step_r(int n, const double *nom, const double *den, const double *z, double *r, const double *dinv,
-                double *partials, double *out, double *alpha, hipStream_t s, const PcgCtl *ctl = nullptr,
+                double *partials, double *out, double *alpha, hipStream_t s, const LoopCtl *ctl = nullptr,
                 const PcgStop *stop = nullptr);
 void pcg_update_xd(int n, const double *nom, const double *den, const double *betanom, double *x, double *d,
-                   const double *r, const double *dinv, hipStream_t s, const PcgCtl *ctl = nullptr);
-void pcg_finish_x(int n, const double *alpha, const double *d, double *x, hipStream_t s, const PcgCtl *ctl);
+                   const double *r, const double *dinv, hipStream_t s, const LoopCtl *ctl = nullptr);
+void pcg_finish_x(int n, const double *alpha, const double *d, double *x, hipStream_t s, const LoopCtl *ctl);
 // a stopping test alone (after a distributed dot's all-reduce)
 void pcg_check(const double *v, const PcgStop &stop, hipStream_t s);
 // saved[i] = v[idx[i]], v[idx[i]] = 0  /  v[idx[i]] = y[idx[i]] = saved[i]
@@ -647,7 +651,7 @@ void ess_restore(int n, const int *idx, const double *saved, double *v, double *
 // ess_restore's blocks: sq_parts[block] = the block's sum of saved^2 (fixed order), ess_parts(n) of them
 int ess_parts(int n);
 // the second pass of a deterministic dot over nparts given partials (+ optional stopping test)
-void dot_final(int nparts, const double *partials, double *out, hipStream_t s, const PcgCtl *ctl = nullptr,
+void dot_final(int nparts, const double *partials, double *out, hipStream_t s, const LoopCtl *ctl = nullptr,
                const PcgStop *stop = nullptr, double *hout = nullptr);
 //   z = dinv .* r  (dinv may be null -> z = r)
 void pcg_precond(int n, const double *dinv, const double *r, double *z, hipStream_t s);
@@ -673,15 +677,10 @@ void sum_partials(int b0, int b1, const int *blocks, const int *runs, const int 
 // ---- vector kernels for the device BiCGSTAB (k_bicgstab.hip) ----
 // BiCGSTABSolver::Mult's iteration (linalg/solvers.cpp:1650-1784) in five vector passes, about 23 vector
 // streams beside its two Mults (one BLAS-1 call per line moves about 30), the same operations per entry
-// in the reference's order.  The loop is driven by the device as the PCG's: its state is BcgCtl (device
-// memory, and a mapped coherent host mirror the host polls), the scalars live in BcgScal, the stopping
-// decisions (bicgstab_stop.hpp) run in bcg_final, and every kernel returns at once when ctl->done is set.
+// in the reference's order.  The loop is driven by the device as the PCG's, on the same LoopCtl (done: BcgDone),
+// the scalars live in BcgScal, the stopping decisions (bicgstab_stop.hpp) run in bcg_final, and every kernel
+// returns at once when ctl->done is set.
 // No atomics: every partial list is parked one per workgroup and summed in a fixed order.
-struct BcgCtl
-{
-   int done, iters, checked, pad;   // BcgDone; final_iter; (mirror) the last iteration whose tests all ran
-   double final;                    // final_norm
-};
 struct BcgScal
 {
    double rho1, rho2, alpha, omega;  // rho_1 = (r~, r) of the running iteration, rho_2, alpha, omega of the last
@@ -702,7 +701,7 @@ struct BcgFinal
 {
    int mode = BCG_FINAL_DOT, it = 0, max_iter = 0;
    double tol_goal = 0.0;
-   BcgCtl *ctl = nullptr, *host = nullptr;
+   LoopCtl *ctl = nullptr, *host = nullptr;
    BcgScal *sc = nullptr;
    double *out = nullptr, *hout = nullptr;
 };
@@ -712,7 +711,7 @@ void bcg_dot(int n, const double *a, const double *b, const double *c, double *p
 // it == 1: p = r; else beta = (rho_1 / rho_2) (alpha / omega), p = r + beta (p - omega v); phat = dinv .* p
 // (dinv null: phat = p)
 void bcg_update_p(int n, int it, const BcgScal *sc, double *p, const double *v, const double *r, const double *dinv,
-                  double *phat, const BcgCtl *ctl, hipStream_t s);
+                  double *phat, const LoopCtl *ctl, hipStream_t s);
 // alpha = rho_1 / (r~, v) (-> sc->alpha); s = r - alpha v into r's storage; shat = dinv .* s (dinv null: shat
 // is not written, s serves); list 0 = the partials of ||s||^2; then bcg_final(f) (BCG_FINAL_S)
 void bcg_update_s(int n, BcgScal *sc, double *r, const double *v, const double *dinv, double *shat, double *partials,
@@ -722,7 +721,7 @@ void bcg_update_s(int n, BcgScal *sc, double *r, const double *v, const double *
 void bcg_update_xr(int n, BcgScal *sc, double *x, const double *phat, const double *shat, double *r, const double *t,
                    const double *rt, double *partials, const BcgFinal &f, hipStream_t s);
 // after the loop: x += alpha phat when it stopped at a ||s|| test
-void bcg_finish_x(int n, const BcgScal *sc, const double *phat, double *x, const BcgCtl *ctl, hipStream_t s);
+void bcg_finish_x(int n, const BcgScal *sc, const double *phat, double *x, const LoopCtl *ctl, hipStream_t s);
 } // namespace kern
 
 } // namespace ecm2

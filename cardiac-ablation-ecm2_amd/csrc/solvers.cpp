@@ -82,58 +82,162 @@ void MemberOp::diagonal(double *d, hipStream_t s)
 }
 
 // ---------------------------------------------------------------------------------------
-// ConstrainedOperator + CGSolver + OperatorJacobiSmoother
+// what the device-driven solvers share: the loop driver, the workspace, the constrained Mult, Jacobi
 // ---------------------------------------------------------------------------------------
 namespace
 {
-// CGSolver's work vectors live across solves (CGSolver::SetOperator allocates them once,
-// solvers.cpp:869-880): one workspace per host thread and device, grown on demand, with a
-// mapped pinned scalar the final-dot kernels write the stopping-test value into.
-struct PCGWork
+// The host side of a device-driven loop (kernels.hpp LoopCtl): the device state and its mapped pinned mirror
+// (coherent: the host polls it while kernels run).  The only place that reads the mirror through volatile.
+class LoopDriver
 {
-   DeviceArray<double> r, d, z, saved, dinv, partials, scal;
-   double *hs = nullptr, *hs_dev = nullptr;
-   DeviceArray<kern::PcgCtl> ctl;                          // the device-driven loop's state
-   kern::PcgCtl *hctl = nullptr, *hctl_dev = nullptr;      // its mapped pinned mirror
-   ~PCGWork()
+public:
+   LoopDriver() : ctl_(1)
    {
-      if (hs) { (void)hipHostFree(hs); }
-      if (hctl) { (void)hipHostFree(hctl); }
+      ECM2_HIP(hipHostMalloc(&mirror_, sizeof(kern::LoopCtl), hipHostMallocMapped | hipHostMallocCoherent));
+      ECM2_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&mirror_dev_), mirror_, 0));
    }
-   void ensure(int n, int n_ess, bool jacobi)
+   ~LoopDriver() { (void)hipHostFree(mirror_); }
+   LoopDriver(const LoopDriver &) = delete;
+   LoopDriver &operator=(const LoopDriver &) = delete;
+   kern::LoopCtl *ctl() { return ctl_.data(); }        // the device state
+   kern::LoopCtl *mirror() { return mirror_dev_; }     // the mirror, as the kernels address it
+   // before a loop's first kernel is enqueued (no kernel of a previous solve writes the mirror any more:
+   // SolverWork's invariant)
+   void reset(hipStream_t s)
+   {
+      ECM2_HIP(hipMemsetAsync(ctl_.data(), 0, sizeof(kern::LoopCtl), s));
+      *mirror_ = kern::LoopCtl{};
+   }
+   // Has the loop stopped at an iteration <= waited?  Waits until the tests of iteration `waited` have run,
+   // without synchronising the stream; the host has enqueued nothing past `waited`.
+   // "At an iteration <= waited", not "done != 0" alone: a stop found in the tail of `waited` carries iters =
+   // waited + 1 (PCG: (A d, d) == 0 or not finite; BiCGSTAB: the next rho_1 == 0), and the PCG finds it in a
+   // kernel that runs after the progress mark of `waited` -- whether done is already set when the host looks
+   // is a matter of timing.  With the iteration in the predicate the answer is not: after such a stop every
+   // caller enqueues iteration waited + 1 (each kernel of it returns at once) and stops at the next call, so
+   // the ranks of a distributed operator issue the same collectives.  No result depends on it: what runs
+   // after the loop (pcg_finish_x, bcg_finish_x) keys on the stop code.
+   bool stopped_by(int waited, hipStream_t s, const char *solver_name)
+   {
+      const volatile kern::LoopCtl *m = mirror_;
+      for (long spin = 1;; spin++)
+      {
+         // (the device writes iters and done before checked: a stop at `waited` is visible once checked says so)
+         if (m->checked >= waited || m->done != 0) { return m->done != 0 && m->iters <= waited; }
+         if (spin % 4096 == 0)
+         {
+            const hipError_t e = hipStreamQuery(s);
+            if (e == hipSuccess && m->checked < waited && m->done == 0)
+            {
+               ECM2_VERIFY(false, ERR_INTERNAL,
+                           "device " << solver_name << " loop: stream idle before the tests of iteration " << waited);
+            }
+            if (e != hipSuccess && e != hipErrorNotReady) { ECM2_HIP(e); }
+         }
+         // back off after a short spin: the host core stays free for RCCL's
+         // proxy and the other ranks' host threads while the device runs the iteration
+         if (spin > 256) { std::this_thread::yield(); }
+      }
+   }
+   // after the loop's last kernel: the stream synchronised, then done, iters and final
+   kern::LoopCtl finish(hipStream_t s)
+   {
+      ECM2_HIP(hipStreamSynchronize(s));
+      const volatile kern::LoopCtl *m = mirror_;
+      kern::LoopCtl end{};
+      end.done = m->done;
+      end.iters = m->iters;
+      end.final = m->final;
+      return end;
+   }
+
+private:
+   DeviceArray<kern::LoopCtl> ctl_;
+   kern::LoopCtl *mirror_ = nullptr, *mirror_dev_ = nullptr;
+};
+
+// CGSolver's and BiCGSTABSolver's work vectors live across solves (CGSolver::SetOperator allocates them once,
+// solvers.cpp:869-880; UpdateVectors, :1579-1604): one workspace per host thread and device for both methods,
+// grown on demand.  Sharing it is safe because every solve ends with the stream synchronised -- the
+// ERR_NUMERIC throws and the early returns included, each of which follows a synchronisation with nothing
+// enqueued after it: when a solve starts, no kernel of the previous one reads a vector here or writes the
+// loop's mirror.
+struct SolverWork
+{
+   // by role: the residual, the direction (PCG's d), the operator's product (PCG's z = A d, BiCGSTAB's v)
+   DeviceArray<double> r, p, ap;
+   DeviceArray<double> rt, phat, t, shat;  // BiCGSTAB alone: r~, M^{-1} p, A shat, M^{-1} s (s lives in r's storage)
+   DeviceArray<double> dinv, saved, partials, scal;  // Jacobi; the constrained Mult's ess entries; sums; PCG's scalars
+   DeviceArray<kern::BcgScal> bcg;                   // BiCGSTAB's scalars
+   double *hs = nullptr, *hs_dev = nullptr;  // mapped pinned scalar the final passes write a read-back value into
+   LoopDriver loop;
+   SolverWork() : scal(4)
+   {
+      ECM2_HIP(hipHostMalloc(&hs, sizeof(double), hipHostMallocMapped));
+      ECM2_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&hs_dev), hs, 0));
+   }
+   ~SolverWork() { (void)hipHostFree(hs); }
+   void ensure(int n, int n_ess, bool jacobi, bool bicgstab, size_t nparts)
    {
       auto grow = [](DeviceArray<double> &a, size_t m) {
          if (a.size() < m) { a.resize(m); }
       };
-      grow(r, std::max(n, 1));
-      grow(d, std::max(n, 1));
-      grow(z, std::max(n, 1));
-      grow(saved, std::max(n_ess, 1));
-      if (jacobi) { grow(dinv, std::max(n, 1)); }
-      grow(partials, kern::kDotPartials);
-      grow(scal, 4);
-      if (!hs)
+      const size_t m = std::max(n, 1);
+      for (DeviceArray<double> *a : {&r, &p, &ap}) { grow(*a, m); }
+      if (bicgstab)
       {
-         ECM2_HIP(hipHostMalloc(&hs, 4 * sizeof(double), hipHostMallocMapped));
-         ECM2_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&hs_dev), hs, 0));
-         // (coherent: the host polls it while kernels run)
-         ECM2_HIP(hipHostMalloc(&hctl, sizeof(kern::PcgCtl), hipHostMallocMapped | hipHostMallocCoherent));
-         ECM2_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&hctl_dev), hctl, 0));
-         ctl.resize(1);
+         for (DeviceArray<double> *a : {&rt, &phat, &t}) { grow(*a, m); }
+         if (jacobi) { grow(shat, m); }
+         if (bcg.size() < 1) { bcg.resize(1); }
       }
+      if (jacobi) { grow(dinv, m); }
+      grow(saved, std::max(n_ess, 1));
+      grow(partials, nparts);
    }
 };
 
-PCGWork &pcg_work()
+SolverWork &solver_work()
 {
-   static thread_local std::vector<std::unique_ptr<PCGWork>> per_device;
+   static thread_local std::vector<std::unique_ptr<SolverWork>> per_device;
    int dev = 0;
    ECM2_HIP(hipGetDevice(&dev));
    if ((int)per_device.size() <= dev) { per_device.resize(dev + 1); }
-   if (!per_device[dev]) { per_device[dev].reset(new PCGWork()); }
+   if (!per_device[dev]) { per_device[dev].reset(new SolverWork()); }
    return *per_device[dev];
 }
+
+// ConstrainedOperator::ConstrainedMult, DIAG_ONE (operator.cpp:586-646): the input's ess entries are zeroed
+// in place for the Mult and restored after (no vector copy); out[ess] = in[ess].  With `en` (an operator that
+// folds its energy, LinOp::energy_parts() of them): the Mult's energy partials of the zeroed input at en, the
+// essential rows' sum of in[ess]^2 behind them.
+struct ConstrainedMult
+{
+   LinOp &A;
+   const int *ess;
+   int n_ess;
+   double *saved;
+   hipStream_t s;
+   void operator()(double *in, double *out, double *en = nullptr) const
+   {
+      kern::ess_save_zero(n_ess, ess, in, saved, s);  // (n_ess == 0: neither kernel is launched)
+      if (en) { A.mult_energy(in, out, en, s); }
+      else { A.mult(in, out, s); }
+      kern::ess_restore(n_ess, ess, saved, in, out, s, en ? en + A.energy_parts() : nullptr);
+   }
+};
+
+// OperatorJacobiSmoother on the constrained operator: dinv = 1 / diag(D), the essential rows' diag 1
+void jacobi_dinv(LinOp &D, const int *ess, int n_ess, double *scratch, double *dinv, hipStream_t s)
+{
+   D.diagonal(scratch, s);
+   if (n_ess) { kern::set_values(n_ess, ess, 1.0, scratch, s); }
+   kern::reciprocal(D.size(), scratch, dinv, s);
+}
 } // namespace
+
+// ---------------------------------------------------------------------------------------
+// ConstrainedOperator + CGSolver + OperatorJacobiSmoother
+// ---------------------------------------------------------------------------------------
 
 PCGResult pcg_solve(LinOp &A, const int *ess, int n_ess, const double *b, double *x, double rel_tol,
                     double abs_tol, int max_iter, bool jacobi, hipStream_t s)
@@ -143,16 +247,22 @@ PCGResult pcg_solve(LinOp &A, const int *ess, int n_ess, const double *b, double
    ECM2_VERIFY(((uintptr_t)x % 16) == 0, ERR_ARG, "PCG: x must be 16-byte aligned (got " << (const void *)x << ")");
    const int n = A.size();
    PCGResult res;
-   PCGWork &w = pcg_work();
-   w.ensure(n, n_ess, jacobi);
-   double *r = w.r.data(), *d = w.d.data(), *z = w.z.data(), *dinv = jacobi ? w.dinv.data() : nullptr;
-   double *partials = w.partials.data();
-   // device scalars; nom and betanom swap roles every iteration (no copy); alpha of the last step
-   double *nom = w.scal.data(), *den = w.scal.data() + 1, *betanom = w.scal.data() + 2, *alpha = w.scal.data() + 3;
    // serial: the final-dot kernel also writes the value into mapped pinned memory, so the
    // stopping test needs only a stream sync; distributed: copy after the all-reduce
    const bool direct = !A.distributed();
-   auto dot = [&](const double *a, const double *bb, double *out, const kern::PcgCtl *c = nullptr) {
+   // den = (A d, d) folded into the Mult where the operator can (serial snapshot forms): the
+   // kernel's element energies sum_e d~_e . A_e d~_e (d~ = d with the ess entries zeroed, as the
+   // constrained Mult sees it) plus the DIAG_ONE rows' sum_ess d_i^2 -- the same value as the dot of
+   // d and A d up to the summation order -- one partial per workgroup, summed in a fixed order by
+   // dot_final: no pass over the two vectors (2 streams and a launch per iteration).
+   const int nen = direct ? A.energy_parts() : 0;
+   SolverWork &w = solver_work();
+   w.ensure(n, n_ess, jacobi, false, std::max({kern::kDotPartials, kern::step_parts(n), nen + kern::ess_parts(n_ess)}));
+   double *r = w.r.data(), *d = w.p.data(), *z = w.ap.data(), *dinv = jacobi ? w.dinv.data() : nullptr;
+   double *partials = w.partials.data();
+   // device scalars; nom and betanom swap roles every iteration (no copy); alpha of the last step
+   double *nom = w.scal.data(), *den = w.scal.data() + 1, *betanom = w.scal.data() + 2, *alpha = w.scal.data() + 3;
+   auto dot = [&](const double *a, const double *bb, double *out, const kern::LoopCtl *c = nullptr) {
       kern::dot(n, a, bb, partials, out, s, direct && !c ? w.hs_dev : nullptr, c);
       A.sum_scalars(out, 1, s);
    };
@@ -161,40 +271,12 @@ PCGResult pcg_solve(LinOp &A, const int *ess, int n_ess, const double *b, double
       ECM2_HIP(hipStreamSynchronize(s));
       return *(volatile double *)w.hs;
    };
-   // ConstrainedOperator::ConstrainedMult, DIAG_ONE (operator.cpp:586-646): the input's
-   // ess entries are zeroed in place for the Mult and restored after (no vector copy);
-   // out[ess] = in[ess]
-   auto cmult = [&](double *in, double *out) {
-      if (n_ess == 0) { A.mult(in, out, s); return; }
-      kern::ess_save_zero(n_ess, ess, in, w.saved.data(), s);
-      A.mult(in, out, s);
-      kern::ess_restore(n_ess, ess, w.saved.data(), in, out, s);
-   };
-   // den = (A d, d) folded into the Mult where the operator can (serial snapshot forms): the
-   // kernel's element energies sum_e d~_e . A_e d~_e (d~ = d with the ess entries zeroed, as the
-   // constrained Mult sees it) plus the DIAG_ONE rows' sum_ess d_i^2 -- the same value as the dot of
-   // d and A d up to the summation order -- one partial per workgroup, summed in a fixed order by
-   // dot_final: no pass over the two vectors (2 streams and a launch per iteration).
-   const int nen = direct ? A.energy_parts() : 0;
-   const int nparts = std::max({kern::kDotPartials, kern::step_parts(n), nen + kern::ess_parts(n_ess)});
-   if ((int)w.partials.size() < nparts)
-   {
-      w.partials.resize(nparts);
-      partials = w.partials.data();
-   }
-   auto cmult_den = [&](double *in, double *out, const kern::PcgCtl *c, const kern::PcgStop *stop) {
-      if (n_ess) { kern::ess_save_zero(n_ess, ess, in, w.saved.data(), s); }
-      A.mult_energy(in, out, partials, s);
-      if (n_ess) { kern::ess_restore(n_ess, ess, w.saved.data(), in, out, s, partials + nen); }
+   const ConstrainedMult cmult{A, ess, n_ess, w.saved.data(), s};
+   auto cmult_den = [&](double *in, double *out, const kern::LoopCtl *c, const kern::PcgStop *stop) {
+      cmult(in, out, partials);
       kern::dot_final(nen + kern::ess_parts(n_ess), partials, den, s, c, stop, c ? nullptr : w.hs_dev);
    };
-   if (jacobi)
-   {
-      // OperatorJacobiSmoother on the constrained operator: ess rows get diag 1
-      A.diagonal(z, s);
-      if (n_ess) { kern::set_values(n_ess, ess, 1.0, z, s); }
-      kern::reciprocal(n, z, dinv, s);
-   }
+   if (jacobi) { jacobi_dinv(A, ess, n_ess, z, dinv, s); }
    if (n) { ECM2_HIP(hipMemcpyAsync(r, b, sizeof(double) * n, hipMemcpyDeviceToDevice, s)); }
    if (n) { ECM2_HIP(hipMemsetAsync(x, 0, sizeof(double) * n, s)); }
    if (jacobi)
@@ -223,10 +305,8 @@ PCGResult pcg_solve(LinOp &A, const int *ess, int n_ess, const double *b, double
    if (nom0 <= r0) { res.converged = true; }
    else
    {
-      // the device-driven loop's state, reset before the read-back below idles the stream (no
-      // kernel of a previous solve writes the mirror any more: every solve ends synchronised)
-      ECM2_HIP(hipMemsetAsync(w.ctl.data(), 0, sizeof(kern::PcgCtl), s));
-      *w.hctl = kern::PcgCtl{};
+      // the device-driven loop's state, reset before the read-back below idles the stream
+      w.loop.reset(s);
       if (nen > 0) { cmult_den(d, z, nullptr, nullptr); }
       else
       {
@@ -246,37 +326,12 @@ PCGResult pcg_solve(LinOp &A, const int *ess, int n_ess, const double *b, double
          // the same iteration on every rank, so the ranks issue the same collectives.  The iterates
          // are CGSolver's (the same operations per entry, in its order; x += alpha d deferred into
          // the next pass that reads d); at most the stopping iteration's Mult runs after the stop.
-         kern::PcgCtl *ctl = w.ctl.data(), *hm = w.hctl;
-         auto vol = [](const int &v) { return *(volatile const int *)&v; };
-         // has the loop stopped at an iteration <= waited?  (waits until the test of `waited` ran)
-         auto stopped_by = [&](int waited) {
-            for (long spin = 1;; spin++)
-            {
-               if (vol(hm->checked) >= waited)
-               {
-                  // (the device writes done before checked: a stop at `waited` is visible now)
-                  return vol(hm->done) != 0 && vol(hm->iters) <= waited;
-               }
-               if (vol(hm->done) != 0) { return vol(hm->iters) <= waited; }
-               if (spin % 4096 == 0)
-               {
-                  const hipError_t e = hipStreamQuery(s);
-                  if (e == hipSuccess && vol(hm->checked) < waited && vol(hm->done) == 0)
-                  {
-                     ECM2_VERIFY(false, ERR_INTERNAL, "device PCG loop: stream idle before the test of iteration " << waited);
-                  }
-                  if (e != hipSuccess && e != hipErrorNotReady) { ECM2_HIP(e); }
-               }
-               // back off after a short spin: the host core stays free for RCCL's
-               // proxy and the other ranks' host threads while the device runs the iteration
-               if (spin > 256) { std::this_thread::yield(); }
-            }
-         };
+         kern::LoopCtl *ctl = w.loop.ctl();
          for (int i = 1;; i++)
          {
-            if (i > 1 && stopped_by(i - 1)) { break; }
+            if (i > 1 && w.loop.stopped_by(i - 1, s, "PCG")) { break; }
             // r -= alpha A d, betanom = r.(M^{-1} r) in one pass, its test
-            const kern::PcgStop stop{r0, i, max_iter, ctl, w.hctl_dev};
+            const kern::PcgStop stop{r0, i, max_iter, ctl, w.loop.mirror()};
             kern::pcg_step_r(n, nom, den, z, r, dinv, partials, betanom, alpha, s, ctl, direct ? &stop : nullptr);
             if (!direct)
             {
@@ -287,7 +342,7 @@ PCGResult pcg_solve(LinOp &A, const int *ess, int n_ess, const double *b, double
             // x += alpha d, d = M^{-1} r + beta d
             kern::pcg_update_xd(n, nom, den, betanom, x, d, r, dinv, s, ctl);
             // z = A d, den = (A d, d) and its test (after ++i: final_iter = i + 1 on a den == 0 stop)
-            const kern::PcgStop dstop{r0, i + 1, max_iter, ctl, w.hctl_dev, betanom, 1};
+            const kern::PcgStop dstop{r0, i + 1, max_iter, ctl, w.loop.mirror(), betanom, 1};
             if (nen > 0) { cmult_den(d, z, ctl, &dstop); }
             else if (direct)
             {
@@ -304,15 +359,14 @@ PCGResult pcg_solve(LinOp &A, const int *ess, int n_ess, const double *b, double
          }
          // the stopping iteration's x += alpha d (a betanom stop)
          kern::pcg_finish_x(n, alpha, d, x, s, ctl);
-         ECM2_HIP(hipStreamSynchronize(s));
-         const int done = *(volatile int *)&hm->done;
-         ECM2_VERIFY(done != kern::PCG_RUNNING, ERR_INTERNAL, "device PCG loop ended without a stop");
-         const double bn = hm->final;
-         ECM2_VERIFY(done != kern::PCG_NONFINITE, ERR_NUMERIC,
-                     "PCG: non-finite (B r, r) or (A d, d) at iteration " << hm->iters << " (" << bn << ")");
+         const kern::LoopCtl end = w.loop.finish(s);
+         ECM2_VERIFY(end.done != kern::PCG_RUNNING, ERR_INTERNAL, "device PCG loop ended without a stop");
+         const double bn = end.final;
+         ECM2_VERIFY(end.done != kern::PCG_NONFINITE, ERR_NUMERIC,
+                     "PCG: non-finite (B r, r) or (A d, d) at iteration " << end.iters << " (" << bn << ")");
          res.final_norm = bn >= 0 ? std::sqrt(bn) : bn;
-         res.iterations = hm->iters;
-         res.converged = done == kern::PCG_CONVERGED;
+         res.iterations = end.iters;
+         res.converged = end.done == kern::PCG_CONVERGED;
       }
    }
    ECM2_HIP(hipStreamSynchronize(s));
@@ -329,59 +383,6 @@ PCGResult pcg_solve(PAForm &A, const int *ess, int n_ess, const double *b, doubl
 // ---------------------------------------------------------------------------------------
 // ConstrainedOperator + BiCGSTABSolver + OperatorJacobiSmoother(second operator)
 // ---------------------------------------------------------------------------------------
-namespace
-{
-// BiCGSTABSolver's work vectors (UpdateVectors, solvers.cpp:1579-1604; s lives in r's storage), as
-// PCGWork: one workspace per host thread and device, grown on demand.
-struct BcgWork
-{
-   DeviceArray<double> r, rt, p, phat, v, shat, t, dinv, saved, partials;
-   DeviceArray<kern::BcgScal> sc;
-   DeviceArray<kern::BcgCtl> ctl;                      // the device-driven loop's state
-   kern::BcgCtl *hctl = nullptr, *hctl_dev = nullptr;  // its mapped pinned mirror (coherent: polled while kernels run)
-   double *hs = nullptr, *hs_dev = nullptr;            // mapped pinned scalar: (r_0, r_0)
-   ~BcgWork()
-   {
-      if (hs) { (void)hipHostFree(hs); }
-      if (hctl) { (void)hipHostFree(hctl); }
-   }
-   void ensure(int n, int n_ess, bool jacobi)
-   {
-      auto grow = [](DeviceArray<double> &a, size_t m) {
-         if (a.size() < m) { a.resize(m); }
-      };
-      const size_t m = std::max(n, 1);
-      for (DeviceArray<double> *a : {&r, &rt, &p, &phat, &v, &t}) { grow(*a, m); }
-      if (jacobi)
-      {
-         grow(shat, m);
-         grow(dinv, m);
-      }
-      grow(saved, std::max(n_ess, 1));
-      grow(partials, 2 * (size_t)kern::bcg_parts(n));
-      if (!hs)
-      {
-         ECM2_HIP(hipHostMalloc(&hs, sizeof(double), hipHostMallocMapped));
-         ECM2_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&hs_dev), hs, 0));
-         ECM2_HIP(hipHostMalloc(&hctl, sizeof(kern::BcgCtl), hipHostMallocMapped | hipHostMallocCoherent));
-         ECM2_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&hctl_dev), hctl, 0));
-         ctl.resize(1);
-         sc.resize(1);
-      }
-   }
-};
-
-BcgWork &bcg_work()
-{
-   static thread_local std::vector<std::unique_ptr<BcgWork>> per_device;
-   int dev = 0;
-   ECM2_HIP(hipGetDevice(&dev));
-   if ((int)per_device.size() <= dev) { per_device.resize(dev + 1); }
-   if (!per_device[dev]) { per_device[dev].reset(new BcgWork()); }
-   return *per_device[dev];
-}
-} // namespace
-
 PCGResult bicgstab_solve(LinOp &A, LinOp *jacobi_of, const int *ess, int n_ess, const double *b, double *x,
                          double rel_tol, double abs_tol, int max_iter, hipStream_t s)
 {
@@ -394,33 +395,19 @@ PCGResult bicgstab_solve(LinOp &A, LinOp *jacobi_of, const int *ess, int n_ess, 
    ECM2_VERIFY(!jacobi_of || jacobi_of->size() == n, ERR_ARG,
                "BiCGSTAB: the preconditioner's operator has size " << jacobi_of->size() << ", the operator " << n);
    PCGResult res;
-   BcgWork &w = bcg_work();
+   SolverWork &w = solver_work();
    const bool jacobi = jacobi_of != nullptr;
-   w.ensure(n, n_ess, jacobi);
-   double *r = w.r.data(), *rt = w.rt.data(), *p = w.p.data(), *phat = w.phat.data(), *v = w.v.data(), *t = w.t.data();
+   w.ensure(n, n_ess, jacobi, true, 2 * (size_t)kern::bcg_parts(n));
+   double *r = w.r.data(), *rt = w.rt.data(), *p = w.p.data(), *phat = w.phat.data(), *v = w.ap.data(), *t = w.t.data();
    double *dinv = jacobi ? w.dinv.data() : nullptr, *shat = jacobi ? w.shat.data() : nullptr;
    double *partials = w.partials.data();
-   kern::BcgScal *sc = w.sc.data();
-   kern::BcgCtl *ctl = w.ctl.data(), *hm = w.hctl;
-   // the loop's state, reset first (no kernel of a previous solve writes the mirror any more: every solve
-   // ends synchronised, an ERR_NUMERIC one included)
-   ECM2_HIP(hipMemsetAsync(ctl, 0, sizeof(kern::BcgCtl), s));
+   kern::BcgScal *sc = w.bcg.data();
+   kern::LoopCtl *ctl = w.loop.ctl();
+   // the loop's state, reset first
+   w.loop.reset(s);
    ECM2_HIP(hipMemsetAsync(sc, 0, sizeof(kern::BcgScal), s));
-   *hm = kern::BcgCtl{};
-   // ConstrainedOperator::ConstrainedMult, DIAG_ONE: pcg_solve's cmult
-   auto cmult = [&](double *in, double *out) {
-      if (n_ess == 0) { A.mult(in, out, s); return; }
-      kern::ess_save_zero(n_ess, ess, in, w.saved.data(), s);
-      A.mult(in, out, s);
-      kern::ess_restore(n_ess, ess, w.saved.data(), in, out, s);
-   };
-   if (jacobi)
-   {
-      // OperatorJacobiSmoother(jacobi_of's diagonal, ess): essential rows get diag 1
-      jacobi_of->diagonal(t, s);
-      if (n_ess) { kern::set_values(n_ess, ess, 1.0, t, s); }
-      kern::reciprocal(n, t, dinv, s);
-   }
+   const ConstrainedMult cmult{A, ess, n_ess, w.saved.data(), s};
+   if (jacobi) { jacobi_dinv(*jacobi_of, ess, n_ess, t, dinv, s); }
    // x = 0, r = b, r~ = r (solvers.cpp:1623-1628)
    if (n)
    {
@@ -431,7 +418,7 @@ PCGResult bicgstab_solve(LinOp &A, LinOp *jacobi_of, const int *ess, int n_ess, 
    // (r~, r) = ||r_0||^2 is also iteration 1's rho_1, summed by the pass that sums (r~, v)
    kern::BcgFinal fin;
    fin.ctl = ctl;
-   fin.host = w.hctl_dev;
+   fin.host = w.loop.mirror();
    fin.sc = sc;
    fin.max_iter = max_iter;
    fin.mode = kern::BCG_FINAL_DOT;
@@ -454,38 +441,13 @@ PCGResult bicgstab_solve(LinOp &A, LinOp *jacobi_of, const int *ess, int n_ess, 
    if (max_iter < 1) { return res; }  // (the loop does not run: not converged, final_norm = ||r_0||)
    fin.tol_goal = tol_goal;
    fin.hout = nullptr;
-   auto vol = [](const int &q) { return *(volatile const int *)&q; };
-   // has the loop stopped at an iteration <= waited?  (waits until the tests of `waited` ran; pcg_solve's)
-   auto stopped_by = [&](int waited) {
-      for (long spin = 1;; spin++)
-      {
-         if (vol(hm->checked) >= waited)
-         {
-            // (the device writes done before checked: a stop at `waited` is visible now)
-            // (a rho_1 == 0 stop found in the tail of `waited` carries final_iter = waited + 1)
-            return vol(hm->done) != 0;
-         }
-         if (vol(hm->done) != 0) { return true; }  // (nothing past `waited` is enqueued yet)
-         if (spin % 4096 == 0)
-         {
-            const hipError_t e = hipStreamQuery(s);
-            if (e == hipSuccess && vol(hm->checked) < waited && vol(hm->done) == 0)
-            {
-               ECM2_VERIFY(false, ERR_INTERNAL, "device BiCGSTAB loop: stream idle before the tests of iteration " << waited);
-            }
-            if (e != hipSuccess && e != hipErrorNotReady) { ECM2_HIP(e); }
-         }
-         // back off after a short spin: the host core stays free while the device runs the iteration
-         if (spin > 256) { std::this_thread::yield(); }
-      }
-   };
    // BiCGSTABSolver's loop (solvers.cpp:1650-1784) driven by the device: the host enqueues iteration i as
    // soon as the last test of i - 1 has run (it polls the mirror's progress mark; no host synchronisation
    // of the stream) and ends at the iteration the device stopped at; at most the stopping iteration's
-   // Mults run after the stop.
+   // Mults run after the stop (a rho_1 == 0 stop carries the next iteration's number: that iteration's too).
    for (int i = 1;; i++)
    {
-      if (i > 1 && stopped_by(i - 1)) { break; }
+      if (i > 1 && w.loop.stopped_by(i - 1, s, "BiCGSTAB")) { break; }
       fin.it = i;
       // p, phat
       kern::bcg_update_p(n, i, sc, p, v, r, dinv, phat, ctl, s);
@@ -508,14 +470,13 @@ PCGResult bicgstab_solve(LinOp &A, LinOp *jacobi_of, const int *ess, int n_ess, 
    }
    // the stopping iteration's x += alpha phat (a ||s|| stop)
    kern::bcg_finish_x(n, sc, phat, x, ctl, s);
-   ECM2_HIP(hipStreamSynchronize(s));
-   const int done = vol(hm->done);
-   ECM2_VERIFY(done != BCG_RUNNING, ERR_INTERNAL, "device BiCGSTAB loop ended without a stop");
-   const double fn = hm->final;
-   ECM2_VERIFY(done != BCG_NONFINITE, ERR_NUMERIC, "BiCGSTAB: resid = " << fn << " at iteration " << hm->iters);
-   res.final_norm = fn;
-   res.iterations = hm->iters;
-   res.converged = bcg_converged(done);
+   const kern::LoopCtl end = w.loop.finish(s);
+   ECM2_VERIFY(end.done != BCG_RUNNING, ERR_INTERNAL, "device BiCGSTAB loop ended without a stop");
+   ECM2_VERIFY(end.done != BCG_NONFINITE, ERR_NUMERIC,
+               "BiCGSTAB: resid = " << end.final << " at iteration " << end.iters);
+   res.final_norm = end.final;
+   res.iterations = end.iters;
+   res.converged = bcg_converged(end.done);
    return res;
 }
 

@@ -122,7 +122,9 @@ struct PCGResult
 };
 
 // Constrained (DIAG_ONE on ess) Jacobi-PCG, x overwritten (iterative_mode = false).
-// Scalars stay on the device; one 8-byte read-back per iteration for the stopping test.
+// Scalars stay on the device and so do the stopping tests: the loop is driven by the device (kernels.hpp
+// LoopCtl), the host polls a mapped mirror's progress mark and synchronises the stream for the two read-backs
+// before the loop and once after it.
 PCGResult pcg_solve(LinOp &A, const int *ess_dev, int n_ess, const double *b, double *x,
                     double rel_tol, double abs_tol, int max_iter, bool jacobi, hipStream_t s);
 PCGResult pcg_solve(PAForm &A, const int *ess_dev, int n_ess, const double *b, double *x,

@@ -1,0 +1,294 @@
+"""The cases of tests/test_gpu_solver_bitwise.py and the recorder of their digests.
+
+    python3 tests/record_solver_digests.py [out.json]
+
+runs every case on cuda:0 through the public Python API, twice, and writes the SHA-256 of the float64
+bytes of each result with the exact iteration count, final norm and converged flag (default:
+tests/golden/solver_digests.json).  A case whose two runs differ is refused: nothing non-deterministic
+enters the set (no case uses scatter = atomic).  The committed file was recorded from the build of the
+commit before the device PCG and the device BiCGSTAB got one loop driver and one workspace
+(csrc/solvers.cpp, LoopCtl): that commit's solvers are the reference the shared pieces must reproduce bit
+for bit.
+
+Inputs use no libm function: the vertices are moved by polynomials, the coefficients are polynomials of
+the coordinates, b, u and the source are seeded uniform draws.  The shapes are the smallest at which each
+shared piece can still go wrong:
+  serial   5 x 4 x 3, p = 2 (693 dofs, odd: the tail lane of the 16-byte passes), mass + diffusion per
+           point: the thread-per-element kernel, EnergyParts() == 0 -- PCG's (A d, d) is a dot pass (the
+           energy-folded path is pinned by ts_epilogue_digests.json); with Jacobi, without, and with no
+           essential dofs (the constrained Mult's shortcut)
+  group    4 x 4 x 8, p = 2, two z slabs as one operator on the concatenated true vectors (not distributed)
+  member   member 0 of the same slabs (structured numbering, overlap): distributed -- the dots through
+           sum_scalars and the stand-alone stopping-test kernel
+  bcg      the serial form + convection (y, -x, x): with Jacobi from the symmetric part, without a
+           preconditioner (s serves as shat), and 4 x 3 x 3, p = 3 (the line kernel) with the convection
+           marked on two of three attributes, without a preconditioner.  (The p = 3 setup with Jacobi is
+           left out: it is not deterministic.  The diagonal of a form on the line kernel is summed by
+           atomic adds onto the L-vector (csrc/k_line.hip, the sum-factorised diagonal), so dinv and with
+           it x differ in the last bits from one process to the next -- three fresh processes of the
+           reference build gave three different digests, while two runs in one process agreed.)
+  ode      one step of SDIRK33 (23) and SDIRK34 (34) on the serial mesh, PCG stages on the symmetric forms
+           and BiCGSTAB stages on the convective ones; 23 / BiCGSTAB with a source
+Each solver setup runs fixed work (rel_tol = 0), max_iter = 1 (the loop ends before any wait) and a
+converging solve.  SEQUENCE: solves of different sizes and methods in one process, each equal to the
+digest of the same solve alone (the workspace they share grows, shrinks in use, and changes method)."""
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+
+DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "solver_digests.json")
+CDT = 0.4359 * 0.05
+CONV_SCALE = 20.0
+MARKER = [0, 1, 1]
+MESHES = {"p2": (5, 4, 3, 2), "p3": (4, 3, 3, 3)}
+# solver runs per setup: name -> (rel_tol, max_iter) for PCG and for BiCGSTAB
+PCG_RUNS = {"fixed": (0.0, 6), "one": (0.0, 1), "conv": (1e-10, 1000)}
+BCG_RUNS = {"fixed": (0.0, 5), "one": (0.0, 1), "conv": (1e-12, 1000)}
+PCG_SERIAL = ["jacobi", "plain", "noess"]
+PCG_PAR = ["group", "member"]
+BCG_SETUPS = ["p2-jacobi", "p2-plain", "p3-plain"]
+ODE_CASES = [(23, "pcg", False), (34, "pcg", False), (23, "bicgstab", True), (34, "bicgstab", False)]
+SEQUENCE = ["bcg-p3-plain-conv", "pcg-jacobi-conv", "pcg-group-conv", "bcg-p2-jacobi-conv", "bcg-p3-plain-conv"]
+_CACHE = {}
+
+
+def all_cases():
+    ids = ["pcg-%s-%s" % (s, r) for s in PCG_SERIAL + PCG_PAR for r in PCG_RUNS]
+    ids += ["bcg-%s-%s" % (s, r) for s in BCG_SETUPS for r in BCG_RUNS]
+    ids += ["ode-%d-%s" % (t, s) for t, s, _ in ODE_CASES]
+    return ids
+
+
+def sha(t):
+    a = np.ascontiguousarray(t.cpu().numpy(), dtype=np.float64)
+    return hashlib.sha256(a.tobytes()).hexdigest()
+
+
+def move(V):
+    V = np.array(V, dtype=np.float64, copy=True)
+    x, y, z = V[:, 0].copy(), V[:, 1].copy(), V[:, 2].copy()
+    V[:, 0] = x + 0.05 * y * (1.0 - y) * z
+    V[:, 1] = y + 0.04 * x * (2.0 - x)
+    V[:, 2] = z + 0.03 * x * y
+    return V
+
+
+def alpha_poly(P):
+    return 2.0 + 0.5 * P[..., 0] * (1.0 - P[..., 1])
+
+
+def beta_poly(P):
+    return 1.0 + 0.5 * P[..., 2]
+
+
+def velocity_poly(P):
+    return np.stack([P[..., 1], -P[..., 0], P[..., 0]], -1)
+
+
+def _cached(key, make):
+    if key not in _CACHE:
+        _CACHE[key] = make()
+    return _CACHE[key]
+
+
+def _dev(torch, a):
+    return torch.as_tensor(np.ascontiguousarray(a)).cuda()
+
+
+def serial_setup(E, torch, name):
+    """(mesh, fes, quadrature points, essential dofs on the device) of a serial mesh."""
+    def make():
+        nx, ny, nz, p = MESHES[name]
+        m = E.Mesh.MakeCartesian3D(nx, ny, nz)
+        m.set_vertices(move(m.vertices()))
+        m.SetAttributes(1 + (np.arange(m.GetNE()) % 3).astype(np.int32))
+        fes = E.H1Space(m, p)
+        ess = torch.as_tensor(np.asarray(fes.boundary_dofs(), dtype=np.int32)).cuda()
+        return m, fes, m.quadrature_points(p + 2), ess
+    return _cached(("serial", name), make)
+
+
+def serial_form(E, torch, name, mass, diff_scale, conv_alpha, marked=False):
+    """mass * Mass(alpha) + Diffusion(diff_scale beta) [+ Convection(v, conv_alpha)], assembled, with the kernel
+    and the dot path asserted."""
+    def make():
+        m, fes, P, _ = serial_setup(E, torch, name)
+        ne = fes.ne
+        f = E.BilinearForm(fes)
+        if mass:
+            f.AddDomainIntegrator(E.MassIntegrator(E.QuadratureCoefficient(_dev(torch, alpha_poly(P).reshape(ne, -1)))))
+        f.AddDomainIntegrator(E.DiffusionIntegrator(E.QuadratureCoefficient(_dev(torch, diff_scale * beta_poly(P).reshape(ne, -1)))))
+        if conv_alpha is not None:
+            ci = E.ConvectionIntegrator(E.VectorCoefficient(_dev(torch, velocity_poly(P))), conv_alpha)
+            if marked:
+                f.AddDomainIntegrator(ci, MARKER)
+            else:
+                f.AddDomainIntegrator(ci)
+        f.Assemble()
+        info = f.info()
+        assert info["kernel"] == (E.KERNEL_TPE if MESHES[name][3] == 2 else E.KERNEL_LINE), info
+        assert f.EnergyParts() == 0 and not f.CoefficientSnapshot()   # (A d, d) by the dot pass
+        kept = int(np.count_nonzero(np.asarray(MARKER)[m.GetAttributes() - 1])) if marked else ne
+        assert f.ConvectionInfo() == ((True, kept, True) if conv_alpha is not None else (False, 0, False)), f.ConvectionInfo()
+        if marked:
+            assert 0 < kept < ne
+        return f
+    return _cached(("form", name, mass, diff_scale, conv_alpha, marked), make)
+
+
+def par_setup(E, torch, kind):
+    """(operator, b, ess) of the 2-slab group (kind "group") or of its member 0 ("member")."""
+    def make():
+        m = E.Mesh.MakeCartesian3D(4, 4, 8)
+        m.set_vertices(move(m.vertices()))
+        member = kind == "member"
+        fes = E.H1Space(m, 2, E.NUMBERING_STRUCTURED if member else E.NUMBERING_ENTITY)
+        er = E.partition_slabs_z(m, 2)
+        forms, parts = [], []
+        for r in range(2):
+            part = E.Partition(fes, er, r, 2, decomposition="overlap")
+            P = E.quadrature_points_subset(m, 4, part.elems)
+            f = E.ParBilinearForm(part)
+            f.AddDomainIntegrator(E.MassIntegrator(E.QuadratureCoefficient(_dev(torch, alpha_poly(P).reshape(part.ne_local, -1)))))
+            f.AddDomainIntegrator(E.DiffusionIntegrator(E.QuadratureCoefficient(_dev(torch, CDT * beta_poly(P).reshape(part.ne_local, -1)))))
+            f.Assemble()
+            forms.append(f)
+            parts.append(part)
+        group = E.ParGroup(forms)
+        bdr = np.asarray(fes.boundary_dofs())
+        bg = np.random.default_rng(23).uniform(0.0, 1.0, fes.ndofs)
+        if member:
+            op = E.Operator(group, member=0)
+            own = parts[0].owned_global
+            assert op.size == len(own) < fes.ndofs
+            b, ess = bg[own], np.nonzero(np.isin(own, bdr))[0]
+        else:
+            op = E.Operator(group)
+            assert op.size == fes.ndofs == 9 * 9 * 17
+            b = np.concatenate([bg[p.owned_global] for p in parts])
+            idx, o = [], 0
+            for p in parts:
+                idx.append(np.nonzero(np.isin(p.owned_global, bdr))[0] + o)
+                o += p.n_owned
+            ess = np.concatenate(idx)
+        assert 0 < len(ess) < op.size
+        return op, _dev(torch, b), _dev(torch, ess.astype(np.int32))
+    return _cached(("par", kind), make)
+
+
+def run_pcg(E, torch, setup, run):
+    rel_tol, max_iter = PCG_RUNS[run]
+    if setup in PCG_SERIAL:
+        _, fes, _, ess = serial_setup(E, torch, "p2")
+        assert fes.ndofs == 693
+        form = serial_form(E, torch, "p2", True, CDT, None)
+        op = _cached(("op", "pcg"), lambda: E.Operator(form))
+        assert isinstance(op.form, E.BilinearForm) and op.size == 693
+        b = _cached(("b", "p2"), lambda: _dev(torch, np.random.default_rng(11).uniform(0.0, 1.0, 693)))
+        ess = None if setup == "noess" else ess
+        jacobi = setup != "plain"
+    else:
+        op, b, ess = par_setup(E, torch, setup)
+        jacobi = True
+    x = torch.full((op.size,), float("nan"), dtype=torch.float64, device="cuda")
+    it, nrm = op.PCG(b, x, ess=ess, rel_tol=rel_tol, max_iter=max_iter, jacobi=jacobi)
+    conv = E.pcg_last_converged()
+    if run == "conv":
+        assert conv and 1 < it < max_iter, (it, conv)
+    else:
+        assert it == max_iter and not conv, (it, conv)
+    return {"x": sha(x), "iterations": it, "final_norm": float(nrm).hex(), "converged": conv}
+
+
+def bcg_setup(E, torch, setup):
+    """(T, jacobi_of or None, b, ess) of a BiCGSTAB setup."""
+    name = setup[:2]
+    marked = name == "p3"
+    _, fes, _, ess = serial_setup(E, torch, name)
+    T = serial_form(E, torch, name, True, CDT, CDT * CONV_SCALE, marked)
+    Top = _cached(("op", "bcgT", name, marked), lambda: E.Operator(T))
+    Sop = None
+    if not setup.endswith("plain"):
+        S = serial_form(E, torch, name, True, CDT, None)
+        Sop = _cached(("op", "bcgS", name), lambda: E.Operator(S))
+    b = _cached(("b", name), lambda: _dev(torch, np.random.default_rng(11).uniform(0.0, 1.0, fes.ndofs)))
+    assert isinstance(Top.form, E.BilinearForm) and Top.size == fes.ndofs
+    return Top, Sop, b, ess
+
+
+def run_bcg(E, torch, setup, run):
+    rel_tol, max_iter = BCG_RUNS[run]
+    Top, Sop, b, ess = bcg_setup(E, torch, setup)
+    x = torch.full((Top.size,), float("nan"), dtype=torch.float64, device="cuda")
+    it, nrm = Top.BiCGSTAB(b, x, ess=ess, rel_tol=rel_tol, max_iter=max_iter, jacobi_of=Sop)
+    conv = E.bicgstab_last_converged()
+    if run == "conv":
+        assert conv and 1 < it < max_iter, (it, conv)
+    else:
+        assert it == max_iter and not conv, (it, conv)
+    return {"x": sha(x), "iterations": it, "final_norm": float(nrm).hex(), "converged": conv}
+
+
+def run_ode(E, torch, ode_type, solver, sourced):
+    _, fes, _, ess = serial_setup(E, torch, "p2")
+    dt = 0.05
+    cdt = E.ode_implicit_coeff(ode_type) * dt
+    bicg = solver == "bicgstab"
+    T = E.Operator(serial_form(E, torch, "p2", True, cdt, cdt * CONV_SCALE if bicg else None))
+    K = E.Operator(serial_form(E, torch, "p2", False, 1.0, CONV_SCALE if bicg else None))
+    X = fes.dof_coords()
+    u = _dev(torch, 37.0 + 20.0 * X[:, 0] * (1.0 - X[:, 1]) + 5.0 * X[:, 2] * X[:, 2])
+    kw = {"source": _dev(torch, np.random.default_rng(31).uniform(0.0, 40.0, fes.ndofs))} if sourced else {}
+    if bicg:
+        kw.update(solver="bicgstab", jacobi_of=E.Operator(serial_form(E, torch, "p2", True, cdt, None)))
+    ns, it, conv = E.ode_step(ode_type, T, K, dt, u, ess=ess, rel_tol=1e-10, max_iter=500, **kw)
+    assert conv and ns == 3 and it > ns, (ns, it, conv)
+    return {"u": sha(u), "solves": ns, "iterations": it, "converged": conv}
+
+
+def run_case(E, torch, cid):
+    kind, rest = cid.split("-", 1)
+    if kind == "ode":
+        t, solver = rest.split("-")
+        return run_ode(E, torch, int(t), solver, dict(((a, b), c) for a, b, c in ODE_CASES)[(int(t), solver)])
+    setup, run = rest.rsplit("-", 1)
+    return run_pcg(E, torch, setup, run) if kind == "pcg" else run_bcg(E, torch, setup, run)
+
+
+def run_sequence(E, torch):
+    """The results of SEQUENCE's solves, run one after the other."""
+    return [run_case(E, torch, cid) for cid in SEQUENCE]
+
+
+def main(argv):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tests"))
+    import helpers  # noqa: F401  (registers the package as ecm2_amd)
+    import torch
+    import ecm2_amd as E
+    E.load_library()
+    out = argv[1] if len(argv) > 1 else DIGESTS
+    digests, refused = {}, []
+    for cid in all_cases():
+        first, second = run_case(E, torch, cid), run_case(E, torch, cid)
+        print(cid, first, flush=True)
+        if first != second:
+            refused.append(cid)
+            print("  REFUSED: the second run gave", second, flush=True)
+            continue
+        digests[cid] = first
+    seq = run_sequence(E, torch)
+    for cid, got in zip(SEQUENCE, seq):
+        assert got == digests[cid], ("sequence", cid, got, digests[cid])
+    print("sequence equals the solves run alone")
+    with open(out, "w") as fh:
+        json.dump(digests, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print("wrote", out, "refused:", refused)
+
+
+if __name__ == "__main__":
+    main(sys.argv)

@@ -1,0 +1,57 @@
+"""GPU: the device PCG and the device BiCGSTAB on their shared loop driver, control struct, partial sums and
+workspace (csrc/solvers.cpp SolverWork / LoopDriver, csrc/dev_common.hpp loop_set_done / park_partial /
+sum_partials_fixed) compute, bit for bit, what they computed as two separate copies of that protocol.
+
+The shared pieces perform the same floating-point additions in the same order, so the comparison is of
+bytes: tests/golden/solver_digests.json holds the SHA-256 of the float64 bytes of every case's x (or u) with
+the exact iteration count, final norm and converged flag, recorded by tests/record_solver_digests.py (which
+also defines the cases, asserts which path ran, and refuses a case whose two runs differ) from the build of
+the commit before the change.  One setup is left out as not deterministic (p = 3 with Jacobi: the line kernel's
+diagonal is summed by atomic adds; the recorder's docstring has the evidence); p = 3 runs without a
+preconditioner.  The sequence test runs solves of both methods and of different sizes one after
+the other in this process, on the workspace they share: each equals the digest of the same solve alone, the
+repeat equals the first."""
+import json
+
+import pytest
+
+import ecm2_amd as E
+import record_solver_digests as R
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _device():
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    E.load_library()
+    yield
+    torch.cuda.synchronize()
+    R._CACHE.clear()
+
+
+@pytest.fixture(scope="module")
+def digests():
+    with open(R.DIGESTS) as fh:
+        return json.load(fh)
+
+
+def test_every_case_has_a_digest(digests):
+    assert sorted(digests) == sorted(R.all_cases())
+
+
+@pytest.mark.parametrize("cid", R.all_cases())
+def test_solver_bitwise(digests, cid):
+    got = R.run_case(E, torch, cid)
+    print(cid, got)
+    assert got == digests[cid], "differs from the recorded bytes"
+
+
+def test_sequence_on_the_shared_workspace(digests):
+    got = R.run_sequence(E, torch)
+    for cid, g in zip(R.SEQUENCE, got):
+        print(cid, g)
+        assert g == digests[cid], cid + " in the sequence differs from the same solve alone"
+    assert got[0] == got[-1]
