@@ -949,6 +949,30 @@ _PAR_SIGS = {
                                               ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                               ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                               ctypes.c_void_p]),
+    "ecm2_chebyshev_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_void_p),
+                                             ctypes.c_void_p]),
+    "ecm2_chebyshev_create_power": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                   ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
+                                                   ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
+    "ecm2_chebyshev_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
+                                           ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
+                                           ctypes.POINTER(ctypes.c_double)]),
+    "ecm2_chebyshev_mult": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "ecm2_smoother_destroy": (None, [ctypes.c_void_p]),
+    "ecm2_power_method": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                         ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
+                                         ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
+                                         ctypes.c_void_p]),
+    "ecm2_operator_pcg_prec": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double,
+                                              ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                              ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]),
+    "ecm2_ode_step_prec": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                          ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                          ctypes.c_void_p]),
     "ecm2_operator_destroy": (None, [ctypes.c_void_p]),
     "ecm2_linear_form_default_q1d": (ctypes.c_int, [ctypes.c_int]),
     "ecm2_linear_form_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
@@ -1285,10 +1309,19 @@ class Operator:
     def Mult(self, x, y, stream=None):
         _check(_par_lib().ecm2_operator_mult(self._h, _dev_ptr(x), _dev_ptr(y), _stream(stream)))
 
-    def PCG(self, b, x, ess=None, rel_tol=1e-12, abs_tol=0.0, max_iter=1000, jacobi=True, stream=None):
-        """ConstrainedOperator(DIAG_ONE) + CGSolver(+OperatorJacobiSmoother); returns (iters, final_norm)."""
+    def PCG(self, b, x, ess=None, rel_tol=1e-12, abs_tol=0.0, max_iter=1000, jacobi=True, stream=None, prec=None):
+        """ConstrainedOperator(DIAG_ONE) + CGSolver(+OperatorJacobiSmoother); returns (iters, final_norm).
+        prec: a ChebyshevSmoother of this operator's size as CGSolver's preconditioner
+        (ecm2_operator_pcg_prec); `jacobi` is then not read."""
         it, nrm = ctypes.c_int(), ctypes.c_double()
         n_ess = 0 if ess is None else int(ess.numel())
+        if prec is not None:
+            if not isinstance(prec, ChebyshevSmoother):
+                raise ECM2Error("prec must be a ChebyshevSmoother")
+            _check(_par_lib().ecm2_operator_pcg_prec(self._h, prec._h, _dev_ptr(ess) if n_ess else None, n_ess,
+                                                     _dev_ptr(b), _dev_ptr(x), rel_tol, abs_tol, max_iter,
+                                                     ctypes.byref(it), ctypes.byref(nrm), _stream(stream)))
+            return it.value, nrm.value
         _check(_par_lib().ecm2_operator_pcg(self._h, _dev_ptr(ess) if n_ess else None, n_ess, _dev_ptr(b), _dev_ptr(x),
                                             rel_tol, abs_tol, max_iter, 1 if jacobi else 0,
                                             ctypes.byref(it), ctypes.byref(nrm), _stream(stream)))
@@ -1317,6 +1350,75 @@ def bicgstab_last_converged() -> bool:
     return bool(_par_lib().ecm2_bicgstab_last_converged())
 
 
+class ChebyshevSmoother:
+    """OperatorChebyshevSmoother (linalg/solvers.hpp:498-586, solvers.cpp:455-658) on the DIAG_ONE constrained
+    operator: y = sum_{k < order} c_k (D^-1 A~)^k D^-1 x, order 1..5.
+    max_eig_estimate: the largest eigenvalue of D^-1 A~; None: the power method's estimate
+    (PowerMethod::EstimateLargestEigenvalue, linalg/operator.cpp:871-928: power_iterations, power_tolerance, and
+    v0, a CUDA start vector that is overwritten, or None for the library's own -- an integer hash of the index,
+    not the reference's seeded rand()).
+    diag_of: the Operator whose diagonal D is taken (None: op itself), as Operator.BiCGSTAB's jacobi_of.
+    The diagonal and the essential list are taken at construction: a form that is assembled again needs a new
+    smoother.  Attributes: order, max_eig, coeffs (the `order` coefficients), power_steps (0: estimate given)."""
+
+    def __init__(self, op, ess=None, order=2, max_eig_estimate=None, diag_of=None, power_iterations=10,
+                 power_tolerance=1e-8, v0=None, stream=None):
+        lib = _par_lib()
+        if not isinstance(op, Operator) or (diag_of is not None and not isinstance(diag_of, Operator)):
+            raise ECM2Error("op and diag_of must be Operators")
+        n_ess = 0 if ess is None else int(ess.numel())
+        h = ctypes.c_void_p()
+        dh = diag_of._h if diag_of is not None else None
+        if max_eig_estimate is not None:
+            _check(lib.ecm2_chebyshev_create(op._h, dh, _dev_ptr(ess) if n_ess else None, n_ess, int(order),
+                                             float(max_eig_estimate), ctypes.byref(h), _stream(stream)))
+        else:
+            if v0 is not None:
+                _check_field(self, v0, op.size)
+            _check(lib.ecm2_chebyshev_create_power(op._h, dh, _dev_ptr(ess) if n_ess else None, n_ess, int(order),
+                                                   int(power_iterations), float(power_tolerance), _dev_ptr(v0),
+                                                   ctypes.byref(h), _stream(stream)))
+        self._h = h
+        self.op, self.diag_of = op, diag_of  # keeps the operator(s) alive while the smoother exists
+        self.size = op.size
+        o, me, ps = ctypes.c_int(), ctypes.c_double(), ctypes.c_int()
+        c = (ctypes.c_double * 5)()
+        _check(lib.ecm2_chebyshev_info(h, ctypes.byref(o), ctypes.byref(me), ctypes.byref(ps), c))
+        self.order, self.max_eig, self.power_steps = o.value, me.value, ps.value
+        self.coeffs = np.array(c[:o.value], dtype=np.float64)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.ecm2_smoother_destroy(self._h)
+            self._h = None
+
+    def Mult(self, x, y, stream=None):
+        """y = S x (OperatorChebyshevSmoother::Mult, solvers.cpp:619-658); x, y distinct CUDA vectors."""
+        _check_field(self, x, self.size)
+        _check_field(self, y, self.size)
+        _check(_par_lib().ecm2_chebyshev_mult(self._h, _dev_ptr(x), _dev_ptr(y), _stream(stream)))
+
+
+def power_method(op, v0, ess=None, diag_of=None, num_steps=10, tol=1e-8, stream=None):
+    """PowerMethod::EstimateLargestEigenvalue (linalg/operator.cpp:871-928) on D^-1 A~ (A~ the DIAG_ONE
+    constrained op, D the diagonal of diag_of or of op, essential rows 1).  v0: the CUDA start vector, overwritten
+    with the last iterate; None: the library's own start vector.  Returns (eigenvalue, steps run)."""
+    if not isinstance(op, Operator) or (diag_of is not None and not isinstance(diag_of, Operator)):
+        raise ECM2Error("op and diag_of must be Operators")
+    if v0 is not None:
+        _check_field(_PowerStart(), v0, op.size)
+    n_ess = 0 if ess is None else int(ess.numel())
+    eig, steps = ctypes.c_double(), ctypes.c_int()
+    _check(_par_lib().ecm2_power_method(op._h, diag_of._h if diag_of is not None else None,
+                                        _dev_ptr(ess) if n_ess else None, n_ess, _dev_ptr(v0), int(num_steps),
+                                        float(tol), ctypes.byref(eig), ctypes.byref(steps), _stream(stream)))
+    return eig.value, steps.value
+
+
+class _PowerStart:
+    """(names power_method's v0 in _check_field's messages)"""
+
+
 ODE_BACKWARD_EULER, ODE_SDIRK23_L, ODE_SDIRK33, ODE_IMPLICIT_MIDPOINT, ODE_SDIRK23, ODE_SDIRK34 = 21, 22, 23, 32, 33, 34
 
 
@@ -1329,7 +1431,7 @@ def ode_implicit_coeff(ode_type: int) -> float:
 
 
 def ode_step(ode_type: int, T: Operator, K: Operator, dt: float, u, ess=None, rel_tol=1e-10, max_iter=500,
-             jacobi=True, stream=None, source=None, solver="pcg", jacobi_of=None):
+             jacobi=True, stream=None, source=None, solver="pcg", jacobi_of=None, prec=None):
     """One implicit step of M du/dt = -K u (ex16 ConductionOperator, slope form) on device vector u
     (in place).  T must be M + c dt K with c = ode_implicit_coeff(ode_type).
     source: a device true-dof vector b in the operators' numbering (e.g. LinearForm.Assemble's),
@@ -1337,11 +1439,24 @@ def ode_step(ode_type: int, T: Operator, K: Operator, dt: float, u, ess=None, re
     solver: "pcg" (the default: symmetric T, `jacobi` its preconditioner switch) or "bicgstab"
     (ecm2_ode_step_bicgstab): T = M + c dt (K_sym + C) and K = K_sym + C carry the ConvectionIntegrator, and
     jacobi_of = the Operator of M + c dt K_sym gives the Jacobi preconditioner (None: none).
+    prec (solver "pcg" only): a ChebyshevSmoother built from T as the stage solves' preconditioner
+    (ecm2_ode_step_prec; T is fixed over the step, so one smoother serves every stage); `jacobi` is not read.
     Returns (stage solves, total solver iterations, converged)."""
     ns, it, conv = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     n_ess = 0 if ess is None else int(ess.numel())
     if solver not in ("pcg", "bicgstab"):
         raise ECM2Error(f"unknown stage solver {solver!r}")
+    if prec is not None:
+        if solver != "pcg" or jacobi_of is not None:
+            raise ECM2Error("prec goes with solver=\"pcg\"")
+        if not isinstance(prec, ChebyshevSmoother):
+            raise ECM2Error("prec must be a ChebyshevSmoother")
+        if source is not None:
+            _check_field(_OdeSource(), source, T.size)
+        _check(_par_lib().ecm2_ode_step_prec(ode_type, T._h, K._h, _dev_ptr(source), prec._h, dt, _dev_ptr(u),
+                                             _dev_ptr(ess) if n_ess else None, n_ess, rel_tol, max_iter,
+                                             ctypes.byref(ns), ctypes.byref(it), ctypes.byref(conv), _stream(stream)))
+        return ns.value, it.value, bool(conv.value)
     if solver == "bicgstab":
         if jacobi_of is not None and not isinstance(jacobi_of, Operator):
             raise ECM2Error("jacobi_of must be an Operator")

@@ -39,6 +39,10 @@ struct ecm2_operator
 {
    std::unique_ptr<ecm2::LinOp> op;
 };
+struct ecm2_smoother
+{
+   std::unique_ptr<ecm2::ChebyshevSmoother> sm;
+};
 struct ecm2_linear_form
 {
    ecm2::LinearForm f;
@@ -1137,6 +1141,98 @@ int ecm2_ode_step_bicgstab(int type, ecm2_operator *T, ecm2_operator *jacobi_of,
       const ecm2::StepStats st = ecm2::ode_step(type, *T->op, *K->op, dt, u, ess, n_ess, rel_tol, max_iter, false,
                                                 S(stream), b, ecm2::STAGE_BICGSTAB,
                                                 jacobi_of ? jacobi_of->op.get() : nullptr);
+      if (solves) { *solves = st.solves; }
+      if (converged) { *converged = st.converged ? 1 : 0; }
+      if (iterations) { *iterations = st.iterations; }
+   });
+}
+
+// ---- OperatorChebyshevSmoother (linalg/solvers.cpp:455-658), PowerMethod (linalg/operator.cpp:871-928) ----
+int ecm2_chebyshev_create(ecm2_operator *A, ecm2_operator *diag_of, const int *ess, int n_ess, int order,
+                          double max_eig_estimate, ecm2_smoother **out, void *stream)
+{
+   return guard([&] {
+      NEED(A); NEED(out);
+      *out = nullptr;
+      ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
+      *out = new ecm2_smoother{std::unique_ptr<ecm2::ChebyshevSmoother>(new ecm2::ChebyshevSmoother(
+         *A->op, diag_of ? diag_of->op.get() : nullptr, ess, n_ess, order, max_eig_estimate, S(stream)))};
+   });
+}
+
+int ecm2_chebyshev_create_power(ecm2_operator *A, ecm2_operator *diag_of, const int *ess, int n_ess, int order,
+                                int power_iterations, double power_tolerance, double *v0, ecm2_smoother **out,
+                                void *stream)
+{
+   return guard([&] {
+      NEED(A); NEED(out);
+      *out = nullptr;
+      ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
+      *out = new ecm2_smoother{std::unique_ptr<ecm2::ChebyshevSmoother>(new ecm2::ChebyshevSmoother(
+         *A->op, diag_of ? diag_of->op.get() : nullptr, ess, n_ess, order, power_iterations, power_tolerance, v0,
+         S(stream)))};
+   });
+}
+
+int ecm2_chebyshev_info(const ecm2_smoother *sm, int *order, double *max_eig, int *power_steps, double coeffs[5])
+{
+   return guard([&] {
+      NEED(sm);
+      if (order) { *order = sm->sm->order(); }
+      if (max_eig) { *max_eig = sm->sm->max_eig(); }
+      if (power_steps) { *power_steps = sm->sm->power_steps(); }
+      if (coeffs)
+      {
+         for (int k = 0; k < 5; k++) { coeffs[k] = sm->sm->coeffs()[k]; }
+      }
+   });
+}
+
+int ecm2_chebyshev_mult(ecm2_smoother *sm, const double *x, double *y, void *stream)
+{
+   return guard([&] { NEED(sm); NEED(x); NEED(y); sm->sm->mult(x, y, S(stream)); });
+}
+
+void ecm2_smoother_destroy(ecm2_smoother *sm) { delete sm; }
+
+int ecm2_power_method(ecm2_operator *A, ecm2_operator *diag_of, const int *ess, int n_ess, double *v0, int num_steps,
+                      double tol, double *eig, int *steps, void *stream)
+{
+   return guard([&] {
+      NEED(A);
+      ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
+      const ecm2::PowerResult r = ecm2::power_method(*A->op, diag_of ? diag_of->op.get() : nullptr, ess, n_ess, v0,
+                                                     num_steps, tol, S(stream));
+      if (eig) { *eig = r.eig; }
+      if (steps) { *steps = r.steps; }
+   });
+}
+
+int ecm2_operator_pcg_prec(ecm2_operator *A, ecm2_smoother *sm, const int *ess, int n_ess, const double *b, double *x,
+                           double rel_tol, double abs_tol, int max_iter, int *iterations, double *final_norm,
+                           void *stream)
+{
+   return guard([&] {
+      NEED(A); NEED(sm); NEED(b); NEED(x);
+      g_pcg_converged = 0;
+      ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
+      const ecm2::PCGResult r = ecm2::pcg_solve_prec(*A->op, *sm->sm, ess, n_ess, b, x, rel_tol, abs_tol, max_iter,
+                                                     S(stream));
+      if (iterations) { *iterations = r.iterations; }
+      if (final_norm) { *final_norm = r.final_norm; }
+      g_pcg_converged = r.converged ? 1 : 0;
+   });
+}
+
+int ecm2_ode_step_prec(int type, ecm2_operator *T, ecm2_operator *K, const double *b, ecm2_smoother *sm, double dt,
+                       double *u, const int *ess, int n_ess, double rel_tol, int max_iter, int *solves, int *iterations,
+                       int *converged, void *stream)
+{
+   return guard([&] {
+      NEED(T); NEED(K); NEED(sm); NEED(u);
+      ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
+      const ecm2::StepStats st = ecm2::ode_step(type, *T->op, *K->op, dt, u, ess, n_ess, rel_tol, max_iter, false,
+                                                S(stream), b, ecm2::STAGE_PCG, nullptr, sm->sm.get());
       if (solves) { *solves = st.solves; }
       if (converged) { *converged = st.converged ? 1 : 0; }
       if (iterations) { *iterations = st.iterations; }

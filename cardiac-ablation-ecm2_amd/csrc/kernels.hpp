@@ -722,6 +722,32 @@ void bcg_update_xr(int n, BcgScal *sc, double *x, const double *phat, const doub
                    const double *rt, double *partials, const BcgFinal &f, hipStream_t s);
 // after the loop: x += alpha phat when it stopped at a ||s|| test
 void bcg_finish_x(int n, const BcgScal *sc, const double *phat, double *x, const LoopCtl *ctl, hipStream_t s);
+
+// ---- vector kernels of OperatorChebyshevSmoother, its power method and the PCG it preconditions (k_cheb.hip) ----
+// The smoother y = sum_k c_k (D^-1 A~)^k D^-1 x term by term (linalg/solvers.cpp:619-658: t *= dinv, y += c_k t):
+//   cheb_first: t = dinv .* x, y = c0 t;
+//   cheb_accum: t = dinv .* h (h = A~ t_prev), y += ck t; with r: the partials of r.y (kDotPartials of them, for
+//               dot_final and its stopping test).
+// t null: the term's t is not stored (the last term).  All vectors 16-byte aligned.
+void cheb_first(int n, const double *dinv, const double *x, double c0, double *t, double *y, hipStream_t s);
+void cheb_accum(int n, const double *dinv, const double *h, double ck, double *t, double *y, hipStream_t s,
+                const double *r = nullptr, double *partials = nullptr, const LoopCtl *ctl = nullptr);
+// CGSolver's update around a stored z = B r (linalg/solvers.cpp:930-990):
+//   pcg_step_r_prec: alpha = nom/den (-> *alpha); r -= alpha ap (ap holds A d); t = dinv .* r; z = c0 t; sum (order
+//                    1): the partials of r.z;
+//   pcg_update_xd_z: x += (nom/den) d; d = z + (betanom/nom) d.
+void pcg_step_r_prec(int n, const double *nom, const double *den, const double *ap, double *r, const double *dinv,
+                     double c0, double *t, double *z, double *partials, double *alpha, bool sum, hipStream_t s,
+                     const LoopCtl *ctl);
+void pcg_update_xd_z(int n, const double *nom, const double *den, const double *betanom, double *x, double *d,
+                     const double *z, hipStream_t s, const LoopCtl *ctl);
+// PowerMethod::EstimateLargestEigenvalue's step on D^-1 A~ (linalg/operator.cpp:871-928): v1 = dinv .* h with the
+// partials of (v0, v1) at partials[0, kDotPartials) and of (v1, v1) behind them; v *= 1 / sqrt(*norm); the
+// default start vector, an integer hash of the index in (0, 1) (k_cheb.hip, k_cheb_fill_hash).
+void cheb_power_pass(int n, const double *dinv, const double *h, const double *v0, double *v1, double *partials,
+                     hipStream_t s);
+void cheb_scale(int n, const double *norm, double *v, hipStream_t s);
+void cheb_fill_hash(int n, double *v, hipStream_t s);
 } // namespace kern
 
 } // namespace ecm2

@@ -1,6 +1,7 @@
 // solvers.cpp -- see solvers.hpp.
 #include "solvers.hpp"
 #include "bicgstab_stop.hpp"
+#include "cheb_coeffs.hpp"
 
 #include <thread>
 
@@ -167,6 +168,7 @@ struct SolverWork
    // by role: the residual, the direction (PCG's d), the operator's product (PCG's z = A d, BiCGSTAB's v)
    DeviceArray<double> r, p, ap;
    DeviceArray<double> rt, phat, t, shat;  // BiCGSTAB alone: r~, M^{-1} p, A shat, M^{-1} s (s lives in r's storage)
+   DeviceArray<double> z, ct;              // the PCG with a smoother alone: z = B r and the smoother's running term
    DeviceArray<double> dinv, saved, partials, scal;  // Jacobi; the constrained Mult's ess entries; sums; PCG's scalars
    DeviceArray<kern::BcgScal> bcg;                   // BiCGSTAB's scalars
    double *hs = nullptr, *hs_dev = nullptr;  // mapped pinned scalar the final passes write a read-back value into
@@ -177,7 +179,7 @@ struct SolverWork
       ECM2_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&hs_dev), hs, 0));
    }
    ~SolverWork() { (void)hipHostFree(hs); }
-   void ensure(int n, int n_ess, bool jacobi, bool bicgstab, size_t nparts)
+   void ensure(int n, int n_ess, bool jacobi, bool bicgstab, size_t nparts, bool prec = false)
    {
       auto grow = [](DeviceArray<double> &a, size_t m) {
          if (a.size() < m) { a.resize(m); }
@@ -191,6 +193,10 @@ struct SolverWork
          if (bcg.size() < 1) { bcg.resize(1); }
       }
       if (jacobi) { grow(dinv, m); }
+      if (prec)
+      {
+         for (DeviceArray<double> *a : {&z, &ct}) { grow(*a, m); }
+      }
       grow(saved, std::max(n_ess, 1));
       grow(partials, nparts);
    }
@@ -481,6 +487,228 @@ PCGResult bicgstab_solve(LinOp &A, LinOp *jacobi_of, const int *ess, int n_ess, 
 }
 
 // ---------------------------------------------------------------------------------------
+// PowerMethod + OperatorChebyshevSmoother + CGSolver(prec = the smoother)
+// ---------------------------------------------------------------------------------------
+static_assert(kChebOk == OK && kChebErrArg == ERR_ARG, "cheb_coeffs.hpp restates Status");
+
+PowerResult power_method(LinOp &A, const double *dinv, const int *ess, int n_ess, double *v0, int num_steps,
+                         double tol, hipStream_t s)
+{
+   ECM2_VERIFY(!A.distributed(), ERR_UNSUPPORTED, "power method: distributed operators are not supported");
+   ECM2_VERIFY(((uintptr_t)v0 % 16) == 0, ERR_ARG, "power method: v0 must be 16-byte aligned (got " << (const void *)v0 << ")");
+   const int n = A.size();
+   SolverWork &w = solver_work();
+   w.ensure(n, n_ess, false, false, std::max(2 * kern::kDotPartials, kern::step_parts(n)));
+   // EstimateLargestEigenvalue's v0, v1 (operator.cpp:875-879) and h = A~ v0
+   double *va = v0 ? v0 : w.r.data(), *vb = w.p.data(), *h = w.ap.data();
+   double *partials = w.partials.data(), *norm = w.scal.data(), *v0v1 = w.scal.data() + 1;
+   const ConstrainedMult cmult{A, ess, n_ess, w.saved.data(), s};
+   if (!v0) { kern::cheb_fill_hash(n, va, s); }
+   kern::dot(n, va, va, partials, norm, s);
+   PowerResult res;
+   for (int iter = 0; iter < num_steps; iter++)
+   {
+      kern::cheb_scale(n, norm, va, s);
+      cmult(va, h);
+      // v1 = D^-1 A~ v0, (v0, v1) and the next step's (v1, v1) in one sweep
+      kern::cheb_power_pass(n, dinv, h, va, vb, partials, s);
+      kern::dot_final(kern::kDotPartials, partials, v0v1, s, nullptr, nullptr, w.hs_dev);
+      kern::dot_final(kern::kDotPartials, partials + kern::kDotPartials, norm, s);
+      ECM2_HIP(hipStreamSynchronize(s));
+      const double eig_new = *(volatile double *)w.hs;
+      ECM2_VERIFY(std::isfinite(eig_new), ERR_NUMERIC, "power method: eigenvalue = " << eig_new << " at step " << iter + 1);
+      const double diff = std::abs((eig_new - res.eig) / res.eig);
+      res.eig = eig_new;
+      res.steps = iter + 1;
+      std::swap(va, vb);
+      if (diff < tol) { break; }
+   }
+   if (v0 && va != v0 && n) { ECM2_HIP(hipMemcpyAsync(v0, va, sizeof(double) * n, hipMemcpyDeviceToDevice, s)); }
+   ECM2_HIP(hipStreamSynchronize(s));
+   return res;
+}
+
+PowerResult power_method(LinOp &A, LinOp *diag_of, const int *ess, int n_ess, double *v0, int num_steps, double tol,
+                         hipStream_t s)
+{
+   LinOp &D = diag_of ? *diag_of : A;
+   ECM2_VERIFY(D.size() == A.size(), ERR_ARG,
+               "power method: the diagonal's operator has size " << D.size() << ", the operator " << A.size());
+   ECM2_VERIFY(!A.distributed() && !D.distributed(), ERR_UNSUPPORTED,
+               "power method: distributed operators are not supported");
+   // (checked again below; here before the diagonal is enqueued)
+   ECM2_VERIFY(((uintptr_t)v0 % 16) == 0, ERR_ARG, "power method: v0 must be 16-byte aligned (got " << (const void *)v0 << ")");
+   DeviceArray<double> scratch(std::max(A.size(), 1)), dinv(std::max(A.size(), 1));
+   jacobi_dinv(D, ess, n_ess, scratch.data(), dinv.data(), s);
+   return power_method(A, dinv.data(), ess, n_ess, v0, num_steps, tol, s);  // (ends synchronised)
+}
+
+void ChebyshevSmoother::setup(LinOp *diag_of, const int *ess_dev, hipStream_t s)
+{
+   // refused before anything is allocated or enqueued
+   ECM2_VERIFY(order_ >= 1 && order_ <= kChebMaxOrder, ERR_ARG,
+               "Chebyshev smoother not implemented for order = " << order_ << " (1.." << kChebMaxOrder << ")");
+   ECM2_VERIFY(n_ess_ >= 0 && (n_ess_ == 0 || ess_dev), ERR_ARG, "Chebyshev smoother: null essential dof list");
+   LinOp &D = diag_of ? *diag_of : A_;
+   ECM2_VERIFY(D.size() == n_, ERR_ARG,
+               "Chebyshev smoother: the diagonal's operator has size " << D.size() << ", the operator " << n_);
+   ECM2_VERIFY(!A_.distributed() && !D.distributed(), ERR_UNSUPPORTED,
+               "Chebyshev smoother: distributed operators are not supported");
+   const size_t m = std::max(n_, 1);
+   dinv_.resize(m);
+   t_.resize(m);
+   h_.resize(m);
+   saved_.resize(std::max(n_ess_, 1));
+   ess_.resize(std::max(n_ess_, 1));
+   if (n_ess_) { ECM2_HIP(hipMemcpyAsync(ess_.data(), ess_dev, sizeof(int) * n_ess_, hipMemcpyDeviceToDevice, s)); }
+   jacobi_dinv(D, ess_.data(), n_ess_, h_.data(), dinv_.data(), s);
+}
+
+ChebyshevSmoother::ChebyshevSmoother(LinOp &A, LinOp *diag_of, const int *ess_dev, int n_ess, int order,
+                                     double max_eig_estimate, hipStream_t s)
+   : A_(A), n_(A.size()), n_ess_(n_ess), order_(order), max_eig_(max_eig_estimate)
+{
+   ECM2_VERIFY(std::isfinite(max_eig_) && max_eig_ != 0.0, ERR_ARG, "Chebyshev smoother: max_eig_estimate = " << max_eig_);
+   setup(diag_of, ess_dev, s);
+   ECM2_VERIFY(cheb_coeffs(order_, max_eig_, coeffs_) == kChebOk, ERR_ARG, "Chebyshev smoother: order " << order_);
+   ECM2_HIP(hipStreamSynchronize(s));
+}
+
+ChebyshevSmoother::ChebyshevSmoother(LinOp &A, LinOp *diag_of, const int *ess_dev, int n_ess, int order,
+                                     int power_iterations, double power_tolerance, double *v0, hipStream_t s)
+   : A_(A), n_(A.size()), n_ess_(n_ess), order_(order)
+{
+   // (power_method's own check, made here before setup() allocates and enqueues)
+   ECM2_VERIFY(((uintptr_t)v0 % 16) == 0, ERR_ARG,
+               "Chebyshev smoother: v0 must be 16-byte aligned (got " << (const void *)v0 << ")");
+   setup(diag_of, ess_dev, s);
+   const PowerResult pr = power_method(A_, dinv_.data(), ess_.data(), n_ess_, v0, power_iterations, power_tolerance, s);
+   max_eig_ = pr.eig;
+   power_steps_ = pr.steps;
+   ECM2_VERIFY(max_eig_ != 0.0, ERR_NUMERIC, "Chebyshev smoother: the power method's estimate is 0");
+   ECM2_VERIFY(cheb_coeffs(order_, max_eig_, coeffs_) == kChebOk, ERR_ARG, "Chebyshev smoother: order " << order_);
+}
+
+void ChebyshevSmoother::mult(const double *x, double *y, hipStream_t s)
+{
+   ECM2_VERIFY(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0, ERR_ARG,
+               "Chebyshev smoother: x and y must be 16-byte aligned (got " << (const void *)x << ", " << (const void *)y << ")");
+   ECM2_VERIFY(x != y, ERR_ARG, "Chebyshev smoother: x and y must be distinct");
+   const ConstrainedMult cmult{A_, ess_.data(), n_ess_, saved_.data(), s};
+   double *t = t_.data(), *h = h_.data();
+   // OperatorChebyshevSmoother::Mult (solvers.cpp:631-657): the term t <- dinv .* (A~ t), y += c_k t
+   kern::cheb_first(n_, dinv_.data(), x, coeffs_[0], order_ > 1 ? t : nullptr, y, s);
+   for (int k = 1; k < order_; k++)
+   {
+      cmult(t, h);
+      kern::cheb_accum(n_, dinv_.data(), h, coeffs_[k], k + 1 < order_ ? t : nullptr, y, s);
+   }
+}
+
+PCGResult pcg_solve_prec(LinOp &A, ChebyshevSmoother &B, const int *ess, int n_ess, const double *b, double *x,
+                         double rel_tol, double abs_tol, int max_iter, hipStream_t s)
+{
+   // refused before anything is enqueued, as in pcg_solve
+   ECM2_VERIFY(((uintptr_t)x % 16) == 0, ERR_ARG, "PCG: x must be 16-byte aligned (got " << (const void *)x << ")");
+   ECM2_VERIFY(!A.distributed(), ERR_UNSUPPORTED, "PCG with a Chebyshev smoother: distributed operators are not supported");
+   const int n = A.size();
+   ECM2_VERIFY(B.size() == n, ERR_ARG, "PCG: the smoother has size " << B.size() << ", the operator " << n);
+   PCGResult res;
+   const int nen = A.energy_parts();  // (A d, d) folded into the Mult where the operator can, as in pcg_solve
+   const int order = B.order();
+   const double *c = B.coeffs(), *dinv = B.dinv();
+   SolverWork &w = solver_work();
+   w.ensure(n, std::max(n_ess, B.n_ess()), false, false,
+            std::max({kern::kDotPartials, kern::step_parts(n), nen + kern::ess_parts(n_ess)}), true);
+   // ap holds A d until the entry pass has consumed it, then the smoother's A~ t
+   double *r = w.r.data(), *d = w.p.data(), *ap = w.ap.data(), *z = w.z.data(), *t = w.ct.data();
+   double *partials = w.partials.data();
+   double *nom = w.scal.data(), *den = w.scal.data() + 1, *betanom = w.scal.data() + 2, *alpha = w.scal.data() + 3;
+   auto readback = [&]() {
+      ECM2_HIP(hipStreamSynchronize(s));
+      return *(volatile double *)w.hs;
+   };
+   const ConstrainedMult cmult{A, ess, n_ess, w.saved.data(), s};
+   const ConstrainedMult bmult{B.op(), B.ess(), B.n_ess(), w.saved.data(), s};
+   auto cmult_den = [&](double *in, double *out, const kern::LoopCtl *ctl, const kern::PcgStop *stop) {
+      if (nen > 0)
+      {
+         cmult(in, out, partials);
+         kern::dot_final(nen + kern::ess_parts(n_ess), partials, den, s, ctl, stop, ctl ? nullptr : w.hs_dev);
+      }
+      else
+      {
+         cmult(in, out);
+         kern::dot(n, in, out, partials, den, s, ctl ? nullptr : w.hs_dev, ctl, stop);
+      }
+   };
+   if (n) { ECM2_HIP(hipMemcpyAsync(r, b, sizeof(double) * n, hipMemcpyDeviceToDevice, s)); }
+   if (n) { ECM2_HIP(hipMemsetAsync(x, 0, sizeof(double) * n, s)); }
+   // z = B r, d = z, nom = (d, r) (solvers.cpp:893-903)
+   B.mult(r, z, s);
+   if (n) { ECM2_HIP(hipMemcpyAsync(d, z, sizeof(double) * n, hipMemcpyDeviceToDevice, s)); }
+   kern::dot(n, d, r, partials, nom, s, w.hs_dev);
+   const double nom0 = readback();
+   ECM2_VERIFY(std::isfinite(nom0), ERR_NUMERIC, "PCG: nom = " << nom0);
+   res.initial_norm = nom0 >= 0 ? std::sqrt(nom0) : nom0;
+   res.final_norm = res.initial_norm;
+   if (nom0 < 0.0)
+   {
+      // the smoother is not positive definite (an estimate far below the largest eigenvalue): not converged,
+      // final_norm = nom (:905-917)
+      res.initial_norm = res.final_norm = nom0;
+      return res;
+   }
+   const double r0 = std::max(nom0 * rel_tol * rel_tol, abs_tol * abs_tol);
+   if (nom0 <= r0)
+   {
+      res.converged = true;
+      return res;
+   }
+   w.loop.reset(s);
+   cmult_den(d, ap, nullptr, nullptr);
+   const double den0 = readback();
+   ECM2_VERIFY(std::isfinite(den0), ERR_NUMERIC, "PCG: den = " << den0);
+   if (den0 == 0.0) { return res; }
+   // CGSolver's loop driven by the device exactly as pcg_solve's (see there); the betanom test runs in the
+   // final pass of the smoother's last term
+   kern::LoopCtl *ctl = w.loop.ctl();
+   for (int i = 1;; i++)
+   {
+      if (i > 1 && w.loop.stopped_by(i - 1, s, "PCG")) { break; }
+      const kern::PcgStop stop{r0, i, max_iter, ctl, w.loop.mirror()};
+      // r -= alpha A d and the smoother's first term: t = dinv .* r, z = c_0 t
+      kern::pcg_step_r_prec(n, nom, den, ap, r, dinv, c[0], order > 1 ? t : nullptr, z, partials, alpha, order == 1, s, ctl);
+      // its further terms: t = dinv .* (A~ t), z += c_k t; the last one sums betanom = (r, z)
+      for (int k = 1; k < order; k++)
+      {
+         const bool last = k + 1 == order;
+         bmult(t, ap);
+         kern::cheb_accum(n, dinv, ap, c[k], last ? nullptr : t, z, s, last ? r : nullptr, partials, ctl);
+      }
+      kern::dot_final(kern::kDotPartials, partials, betanom, s, ctl, &stop);
+      if (i >= max_iter) { break; }
+      // x += alpha d, d = z + beta d
+      kern::pcg_update_xd_z(n, nom, den, betanom, x, d, z, s, ctl);
+      // ap = A d, den = (A d, d) and its test (after ++i: final_iter = i + 1 on a den == 0 stop)
+      const kern::PcgStop dstop{r0, i + 1, max_iter, ctl, w.loop.mirror(), betanom, 1};
+      cmult_den(d, ap, ctl, &dstop);
+      std::swap(nom, betanom);  // nom <- betanom
+   }
+   // the stopping iteration's x += alpha d (a betanom stop)
+   kern::pcg_finish_x(n, alpha, d, x, s, ctl);
+   const kern::LoopCtl end = w.loop.finish(s);
+   ECM2_VERIFY(end.done != kern::PCG_RUNNING, ERR_INTERNAL, "device PCG loop ended without a stop");
+   const double bn = end.final;
+   ECM2_VERIFY(end.done != kern::PCG_NONFINITE, ERR_NUMERIC,
+               "PCG: non-finite (B r, r) or (A d, d) at iteration " << end.iters << " (" << bn << ")");
+   res.final_norm = bn >= 0 ? std::sqrt(bn) : bn;
+   res.iterations = end.iters;
+   res.converged = end.done == kern::PCG_CONVERGED;
+   return res;
+}
+
+// ---------------------------------------------------------------------------------------
 // SDIRK family (slope form, ImplicitVarType::SLOPE) on an ex16-style conduction operator
 // ---------------------------------------------------------------------------------------
 namespace
@@ -519,10 +747,11 @@ double ode_implicit_coeff(int type)
 
 StepStats ode_step(int type, LinOp &T, LinOp &K, double dt, double *u, const int *ess, int n_ess,
                    double rel_tol, int max_iter, bool jacobi, hipStream_t s, const double *b, int solver,
-                   LinOp *jacobi_of)
+                   LinOp *jacobi_of, ChebyshevSmoother *prec)
 {
    ECM2_VERIFY(ode_implicit_supported(type), ERR_ARG, "unsupported implicit ODE solver type " << type);
    ECM2_VERIFY(solver == STAGE_PCG || solver == STAGE_BICGSTAB, ERR_ARG, "unknown stage solver " << solver);
+   ECM2_VERIFY(!prec || solver == STAGE_PCG, ERR_ARG, "a Chebyshev smoother goes with the PCG stage solver");
    ECM2_VERIFY(T.size() == K.size(), ERR_ARG, "T and K sizes differ");
    const int n = T.size();
    StepStats st;
@@ -535,7 +764,8 @@ StepStats ode_step(int type, LinOp &T, LinOp &K, double dt, double *u, const int
       if (n_ess) { kern::set_values(n_ess, ess, 0.0, rhs.data(), s); }
       const PCGResult r = solver == STAGE_BICGSTAB
                              ? bicgstab_solve(T, jacobi_of, ess, n_ess, rhs.data(), kk, rel_tol, 0.0, max_iter, s)
-                             : pcg_solve(T, ess, n_ess, rhs.data(), kk, rel_tol, 0.0, max_iter, jacobi, s);
+                          : prec ? pcg_solve_prec(T, *prec, ess, n_ess, rhs.data(), kk, rel_tol, 0.0, max_iter, s)
+                                 : pcg_solve(T, ess, n_ess, rhs.data(), kk, rel_tol, 0.0, max_iter, jacobi, s);
       st.solves++;
       st.iterations += r.iterations;
       st.max_iterations = std::max(st.max_iterations, r.iterations);

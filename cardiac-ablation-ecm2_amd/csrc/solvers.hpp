@@ -9,6 +9,8 @@
 //   CGSolver::Mult                             linalg/solvers.cpp:869-1004
 //   BiCGSTABSolver::Mult                       linalg/solvers.cpp:1579-1805
 //   OperatorJacobiSmoother (PA diagonal)       linalg/solvers.hpp:421, bilinearform_ext.cpp:370-454
+//   OperatorChebyshevSmoother                  linalg/solvers.hpp:498-586, solvers.cpp:455-658
+//   PowerMethod::EstimateLargestEigenvalue     linalg/operator.cpp:871-928
 //   parallel dot (MPI_Allreduce)               linalg/hypre / InnerProduct(comm, ...)
 //   BackwardEuler / SDIRK23 / SDIRK33 / ImplicitMidpoint / SDIRK34 ::Step
 //                                              linalg/ode.cpp:682-859, selection :77-91
@@ -144,6 +146,73 @@ PCGResult pcg_solve(PAForm &A, const int *ess_dev, int n_ess, const double *b, d
 PCGResult bicgstab_solve(LinOp &A, LinOp *jacobi_of, const int *ess_dev, int n_ess, const double *b, double *x,
                          double rel_tol, double abs_tol, int max_iter, hipStream_t s);
 
+// PowerMethod::EstimateLargestEigenvalue (linalg/operator.cpp:871-928) on D^-1 A~, A~ the DIAG_ONE constrained A
+// and dinv a device vector (1 / diag, essential rows 1): each step normalises v0 (v0 *= 1 / sqrt((v0, v0))),
+// applies v1 = dinv .* (A~ v0), takes eig_new = (v0, v1), forms diff = |(eig_new - eig) / eig| with eig starting
+// at 1, swaps and breaks on diff < tol -- one host read-back per step ((v1, v1), the next step's norm, is summed
+// by the pass that sums (v0, v1)).  v0 (device, A.size(), 16-byte aligned: ERR_ARG otherwise): the start vector
+// on entry, the last iterate (not normalised) on return; null: the library's own, filled from an integer hash
+// of the index in (0, 1) (kern::cheb_fill_hash) -- the reference's Vector::Randomize(seed) draws from glibc's
+// rand(), which is not reproduced.  A non-finite eigenvalue: ERR_NUMERIC.  Distributed operators: ERR_UNSUPPORTED.
+struct PowerResult
+{
+   double eig = 1.0;
+   int steps = 0;
+};
+PowerResult power_method(LinOp &A, const double *dinv, const int *ess_dev, int n_ess, double *v0, int num_steps,
+                         double tol, hipStream_t s);
+// ... with dinv taken from diag_of's diagonal (null: A's), essential rows 1, as the smoother takes it
+PowerResult power_method(LinOp &A, LinOp *diag_of, const int *ess_dev, int n_ess, double *v0, int num_steps,
+                         double tol, hipStream_t s);
+
+// OperatorChebyshevSmoother (linalg/solvers.hpp:498-586, solvers.cpp:455-658) on the DIAG_ONE constrained
+// operator A~: y = sum_{k < order} c_k (D^-1 A~)^k D^-1 x, the coefficients from cheb_coeffs.hpp (Setup,
+// :538-617), Mult's operations per entry in the reference's order (:619-658), iterative_mode = false.
+// diag_of (null: A itself): the operator whose diagonal D is taken, of A's size (as bicgstab_solve's jacobi_of).
+// The diagonal is taken at construction (dinv = 1 / diag, essential rows 1) and so is the essential list (a
+// copy): a form that is assembled again with other coefficients needs a new smoother.  The operator(s) must
+// outlive the smoother.  order outside 1..5: ERR_ARG (the reference aborts).  Distributed operators
+// (distributed() == true): ERR_UNSUPPORTED.  Two applications are bitwise equal.
+class ChebyshevSmoother
+{
+public:
+   // a given estimate of the largest eigenvalue of D^-1 A~
+   ChebyshevSmoother(LinOp &A, LinOp *diag_of, const int *ess_dev, int n_ess, int order, double max_eig_estimate,
+                     hipStream_t s);
+   // the estimate from power_method (the reference's defaults: 10 iterations, tolerance 1e-8); v0 as there
+   ChebyshevSmoother(LinOp &A, LinOp *diag_of, const int *ess_dev, int n_ess, int order, int power_iterations,
+                     double power_tolerance, double *v0, hipStream_t s);
+   int size() const { return n_; }
+   int order() const { return order_; }
+   double max_eig() const { return max_eig_; }
+   int power_steps() const { return power_steps_; }  // (0: the estimate was given)
+   const double *coeffs() const { return coeffs_; }
+   // y = S x (x, y device vectors of size(), 16-byte aligned and distinct: ERR_ARG otherwise)
+   void mult(const double *x, double *y, hipStream_t s);
+   // what pcg_solve_prec's fused passes take
+   LinOp &op() { return A_; }
+   const double *dinv() const { return dinv_.data(); }
+   const int *ess() const { return ess_.data(); }
+   int n_ess() const { return n_ess_; }
+
+private:
+   void setup(LinOp *diag_of, const int *ess_dev, hipStream_t s);
+   LinOp &A_;
+   int n_, n_ess_, order_;
+   double max_eig_ = 0.0, coeffs_[5] = {};
+   int power_steps_ = 0;
+   DeviceArray<int> ess_;
+   DeviceArray<double> dinv_, t_, h_, saved_;  // 1 / diag; the term (D^-1 A~)^k D^-1 x, A~ of it, its ess entries
+};
+
+// CGSolver::Mult (linalg/solvers.cpp:869-1004) with prec = B on the constrained A, x overwritten: pcg_solve's
+// loop (the same device-driven stops: (B r, r) < 0 before or inside the loop, (A d, d) == 0, non-finite ->
+// ERR_NUMERIC, converged, max_iter; the same folded (A d, d) where A offers it; the same deferred x += alpha d)
+// with z = B r stored: the smoother's first term in the pass that updates r, its last in the pass that sums
+// (r, z).  B must be of A's size (ERR_ARG); x 16-byte aligned (ERR_ARG); distributed operators: ERR_UNSUPPORTED.
+PCGResult pcg_solve_prec(LinOp &A, ChebyshevSmoother &B, const int *ess_dev, int n_ess, const double *b, double *x,
+                         double rel_tol, double abs_tol, int max_iter, hipStream_t s);
+
 // ODESolver::SelectImplicit numbering (ode.cpp:77-91): 21 BackwardEuler, 22 SDIRK23(L-stable),
 // 23 SDIRK33, 32 ImplicitMidpoint, 33 SDIRK23 (A-stable, order 3), 34 SDIRK34.
 bool ode_implicit_supported(int type);
@@ -166,9 +235,11 @@ struct StepStats
 // STAGE_BICGSTAB: bicgstab_solve with jacobi_of -- the caller assembles T = M + c*dt*(K_sym + C) and
 // K = K_sym + C with the convection inside both, and passes jacobi_of = M + c*dt*K_sym (null: none;
 // `jacobi` is not read).
+// prec (STAGE_PCG only, ERR_ARG otherwise): the stage solves run pcg_solve_prec with it and `jacobi` is not
+// read; T is fixed over a step, so one smoother built from T serves every stage.
 enum StageSolver : int { STAGE_PCG = 0, STAGE_BICGSTAB = 1 };
 StepStats ode_step(int type, LinOp &T, LinOp &K, double dt, double *u, const int *ess_dev, int n_ess,
                    double rel_tol, int max_iter, bool jacobi, hipStream_t s, const double *b = nullptr,
-                   int solver = STAGE_PCG, LinOp *jacobi_of = nullptr);
+                   int solver = STAGE_PCG, LinOp *jacobi_of = nullptr, ChebyshevSmoother *prec = nullptr);
 
 } // namespace ecm2

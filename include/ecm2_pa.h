@@ -490,6 +490,58 @@ int ecm2_bicgstab_last_converged(void);
 int ecm2_ode_step_bicgstab(int type, ecm2_operator *T, ecm2_operator *jacobi_of, ecm2_operator *K, const double *b /* NULL */,
                            double dt, double *u, const int *ess, int n_ess, double rel_tol, int max_iter,
                            int *solves, int *iterations, int *converged, void *stream);
+
+/* ------------------------------------------------------------------------ */
+/* OperatorChebyshevSmoother (linalg/solvers.hpp:498-586, solvers.cpp:455-658), */
+/* its eigenvalue estimate (PowerMethod::EstimateLargestEigenvalue,            */
+/* linalg/operator.cpp:871-928) and CGSolver::Mult (solvers.cpp:869-1004) with */
+/* the smoother as its preconditioner                                          */
+/* ------------------------------------------------------------------------ */
+/* The smoother y = sum_{k < order} c_k (D^-1 A~)^k D^-1 x on the DIAG_ONE constrained operator A~ (ess: device
+ * int [n_ess], copied), D the diagonal of diag_of (NULL: of A; an operator of A's size, ECM2_ERR_ARG otherwise,
+ * as ecm2_operator_bicgstab's jacobi_of) with the essential rows 1.  The diagonal is taken here: a form that is
+ * assembled again needs a new smoother.  A (and diag_of) must outlive it.  order 1..5 (Setup,
+ * solvers.cpp:538-617; any other: ECM2_ERR_ARG, where the reference aborts).  Serial forms and loopback groups;
+ * an operator whose dots need communication (an RCCL rank, a group member): ECM2_ERR_UNSUPPORTED. */
+typedef struct ecm2_smoother ecm2_smoother;
+/* OperatorChebyshevSmoother(oper, d, ess_tdofs, order, max_eig_estimate) (solvers.cpp:455-469). */
+int ecm2_chebyshev_create(ecm2_operator *A, ecm2_operator *diag_of /* NULL: A */, const int *ess, int n_ess, int order,
+                          double max_eig_estimate, ecm2_smoother **out, void *stream);
+/* OperatorChebyshevSmoother(oper, d, ess_tdofs, order, power_iterations, power_tolerance) (solvers.cpp:480-514;
+ * the reference's defaults 10 and 1e-8): max_eig from ecm2_power_method (operator.cpp:871-928) on D^-1 A~.  v0 (device, 16-byte aligned,
+ * or NULL): as ecm2_power_method's. */
+int ecm2_chebyshev_create_power(ecm2_operator *A, ecm2_operator *diag_of /* NULL: A */, const int *ess, int n_ess,
+                                int order, int power_iterations, double power_tolerance, double *v0 /* NULL */,
+                                ecm2_smoother **out, void *stream);
+/* order, the eigenvalue estimate, the power steps run (0: the estimate was given) and the coefficients
+ * c_0 .. c_{order-1} (the rest 0) of Setup (solvers.cpp:538-617); any pointer may be NULL. */
+int ecm2_chebyshev_info(const ecm2_smoother *sm, int *order, double *max_eig, int *power_steps, double coeffs[5]);
+/* OperatorChebyshevSmoother::Mult (solvers.cpp:619-658), iterative_mode = false: y = S x, x and y distinct device
+ * vectors of the operator's size, 16-byte aligned (ECM2_ERR_ARG otherwise).  Two calls are bitwise equal. */
+int ecm2_chebyshev_mult(ecm2_smoother *sm, const double *x, double *y, void *stream);
+void ecm2_smoother_destroy(ecm2_smoother *sm);
+/* PowerMethod::EstimateLargestEigenvalue (linalg/operator.cpp:871-928) on D^-1 A~ (A~, D as above), seed = 0:
+ * v0 (device, A's size, 16-byte aligned) holds the start vector on entry and the last iterate on return; NULL:
+ * the library's own start vector, an integer hash of the index in (0, 1) (the reference's seeded glibc rand()
+ * is not reproduced).  At most num_steps steps, ended when |(eig_new - eig) / eig| < tol (eig starts at 1);
+ * *steps = the steps run.  A non-finite eigenvalue: ECM2_ERR_NUMERIC. */
+int ecm2_power_method(ecm2_operator *A, ecm2_operator *diag_of /* NULL: A */, const int *ess, int n_ess,
+                      double *v0 /* in: start, out: last iterate; NULL */, int num_steps, double tol, double *eig,
+                      int *steps, void *stream);
+/* ecm2_operator_pcg with prec = the smoother (CGSolver::Mult, solvers.cpp:869-1004; the smoother of A's size,
+ * ECM2_ERR_ARG otherwise): the same stops, read-backs and results as there -- (B r, r) < 0 before the loop
+ * (0 iterations, final_norm = the negative (B r, r)) or inside it and (A d, d) == 0 stop not converged; a
+ * non-finite (B r, r) or (A d, d) returns ECM2_ERR_NUMERIC.  ecm2_pcg_last_converged reports it.  x must be
+ * 16-byte aligned (ECM2_ERR_ARG).  Operators whose dots need communication: ECM2_ERR_UNSUPPORTED. */
+int ecm2_operator_pcg_prec(ecm2_operator *A, ecm2_smoother *sm, const int *ess, int n_ess, const double *b, double *x,
+                           double rel_tol, double abs_tol, int max_iter, int *iterations, double *final_norm,
+                           void *stream);
+/* ecm2_ode_step_source whose stage solves run ecm2_operator_pcg_prec with sm, a smoother built from T (fixed
+ * over the step, so one smoother serves every stage; CGSolver::Mult solvers.cpp:869-1004 with
+ * OperatorChebyshevSmoother::Mult solvers.cpp:619-658).  b == NULL: no source. */
+int ecm2_ode_step_prec(int type, ecm2_operator *T, ecm2_operator *K, const double *b /* NULL */, ecm2_smoother *sm,
+                       double dt, double *u, const int *ess, int n_ess, double rel_tol, int max_iter, int *solves,
+                       int *iterations, int *converged, void *stream);
 void ecm2_operator_destroy(ecm2_operator *op);
 
 /* ------------------------------------------------------------------------ */
