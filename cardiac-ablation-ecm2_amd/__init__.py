@@ -973,6 +973,23 @@ _PAR_SIGS = {
                                           ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                           ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                           ctypes.c_void_p]),
+    "ecm2_transfer_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "ecm2_transfer_mult": (ctypes.c_int, [ctypes.c_void_p] * 4),
+    "ecm2_transfer_mult_transpose": (ctypes.c_int, [ctypes.c_void_p] * 4),
+    "ecm2_transfer_info": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_int)] * 5
+                           + [ctypes.POINTER(ctypes.c_long)]),
+    "ecm2_transfer_destroy": (None, [ctypes.c_void_p]),
+    "ecm2_multigrid_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_void_p)]),
+    "ecm2_multigrid_set_coarse_pcg": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_int]),
+    "ecm2_multigrid_mult": (ctypes.c_int, [ctypes.c_void_p] * 4),
+    "ecm2_multigrid_destroy": (None, [ctypes.c_void_p]),
+    "ecm2_operator_pcg_mg": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double,
+                                            ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                            ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]),
     "ecm2_operator_destroy": (None, [ctypes.c_void_p]),
     "ecm2_linear_form_default_q1d": (ctypes.c_int, [ctypes.c_int]),
     "ecm2_linear_form_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
@@ -1311,16 +1328,17 @@ class Operator:
 
     def PCG(self, b, x, ess=None, rel_tol=1e-12, abs_tol=0.0, max_iter=1000, jacobi=True, stream=None, prec=None):
         """ConstrainedOperator(DIAG_ONE) + CGSolver(+OperatorJacobiSmoother); returns (iters, final_norm).
-        prec: a ChebyshevSmoother of this operator's size as CGSolver's preconditioner
-        (ecm2_operator_pcg_prec); `jacobi` is then not read."""
+        prec: a ChebyshevSmoother of this operator's size (ecm2_operator_pcg_prec) or a Multigrid whose finest
+        level has it (ecm2_operator_pcg_mg) as CGSolver's preconditioner; `jacobi` is then not read."""
         it, nrm = ctypes.c_int(), ctypes.c_double()
         n_ess = 0 if ess is None else int(ess.numel())
         if prec is not None:
-            if not isinstance(prec, ChebyshevSmoother):
-                raise ECM2Error("prec must be a ChebyshevSmoother")
-            _check(_par_lib().ecm2_operator_pcg_prec(self._h, prec._h, _dev_ptr(ess) if n_ess else None, n_ess,
-                                                     _dev_ptr(b), _dev_ptr(x), rel_tol, abs_tol, max_iter,
-                                                     ctypes.byref(it), ctypes.byref(nrm), _stream(stream)))
+            if not isinstance(prec, (ChebyshevSmoother, Multigrid)):
+                raise ECM2Error("prec must be a ChebyshevSmoother or a Multigrid")
+            lib = _par_lib()
+            solve = lib.ecm2_operator_pcg_mg if isinstance(prec, Multigrid) else lib.ecm2_operator_pcg_prec
+            _check(solve(self._h, prec._h, _dev_ptr(ess) if n_ess else None, n_ess, _dev_ptr(b), _dev_ptr(x), rel_tol,
+                         abs_tol, max_iter, ctypes.byref(it), ctypes.byref(nrm), _stream(stream)))
             return it.value, nrm.value
         _check(_par_lib().ecm2_operator_pcg(self._h, _dev_ptr(ess) if n_ess else None, n_ess, _dev_ptr(b), _dev_ptr(x),
                                             rel_tol, abs_tol, max_iter, 1 if jacobi else 0,
@@ -1397,6 +1415,96 @@ class ChebyshevSmoother:
         _check_field(self, x, self.size)
         _check_field(self, y, self.size)
         _check(_par_lib().ecm2_chebyshev_mult(self._h, _dev_ptr(x), _dev_ptr(y), _stream(stream)))
+
+
+class PRefinementTransfer:
+    """TensorProductPRefinementTransferOperator(lfes, hfes) (fem/transfer.cpp:2223-2592) between two H1Spaces of
+    orders lfes.order < hfes.order (1..4) on the same mesh, in either numbering: Mult prolongs a coarse L-vector,
+    MultTranspose restricts a fine one.  Only the spaces' gather maps are read."""
+
+    def __init__(self, lfes, hfes):
+        if not isinstance(lfes, H1Space) or not isinstance(hfes, H1Space):
+            raise ECM2Error("lfes and hfes must be H1Spaces")
+        if lfes.ne != hfes.ne:
+            err = ECM2Error(f"ecm2 error 1: transfer: the spaces have {lfes.ne} and {hfes.ne} elements")
+            err.code = 1
+            raise err
+        gl, gh = lfes.gather_map(), hfes.gather_map()
+        h = ctypes.c_void_p()
+        _check(_par_lib().ecm2_transfer_create(lfes.ne, lfes.order, lfes.ndofs, _np_ptr(gl), hfes.order, hfes.ndofs,
+                                               _np_ptr(gh), ctypes.byref(h)))
+        self._h = h
+        self.width, self.height = lfes.ndofs, hfes.ndofs
+        pb = ctypes.c_long()
+        _check(_lib.ecm2_transfer_info(h, None, None, None, None, None, ctypes.byref(pb)))
+        self.plan_bytes = pb.value
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.ecm2_transfer_destroy(self._h)
+            self._h = None
+
+    def Mult(self, x, y, stream=None):
+        """y (fine) = P x (coarse); y is overwritten."""
+        _check_field(self, x, self.width)
+        _check_field(self, y, self.height)
+        _check(_par_lib().ecm2_transfer_mult(self._h, _dev_ptr(x), _dev_ptr(y), _stream(stream)))
+
+    def MultTranspose(self, x, y, stream=None):
+        """y (coarse) = P^T x (fine); y is overwritten."""
+        _check_field(self, x, self.height)
+        _check_field(self, y, self.width)
+        _check(_par_lib().ecm2_transfer_mult_transpose(self._h, _dev_ptr(x), _dev_ptr(y), _stream(stream)))
+
+
+class Multigrid:
+    """Multigrid's V-cycle (fem/multigrid.cpp:106-232) as GeometricMultigrid sets it up (:296-309: the
+    prolongations' essential rows and columns removed) over levels 0 (coarsest) .. L - 1: ops, smoothers (a
+    ChebyshevSmoother per level, built on that level's Operator and essential list), transfers (L - 1
+    PRefinementTransfers, level k -> k + 1), ess (a CUDA int32 tensor or None per level; copied).
+    coarse_pcg: None -- the coarsest level's smoother applied once -- or (rel_tol, max_iter): a constrained
+    Jacobi-PCG there (examples/ex26.cpp: (1e-2, 200)).  Mult: one cycle from a zero guess."""
+
+    def __init__(self, ops, smoothers, transfers, ess, pre=1, post=1, coarse_pcg=None):
+        lib = _par_lib()
+        L = len(ops)
+        if any(not isinstance(o, Operator) for o in ops) or any(not isinstance(s, ChebyshevSmoother) for s in smoothers) \
+                or any(not isinstance(t, PRefinementTransfer) for t in transfers):
+            raise ECM2Error("ops, smoothers and transfers must be Operators, ChebyshevSmoothers and PRefinementTransfers")
+        ess = [None] * L if ess is None else list(ess)
+        # the C entry reads nlevels entries of every array (nlevels - 1 transfers): checked here, before the call
+        if L < 1 or len(smoothers) != L or len(ess) != L or len(transfers) != L - 1:
+            err = ECM2Error(f"ecm2 error 1: multigrid: {L} levels need {L} smoothers and essential lists and "
+                            f"{max(L - 1, 0)} transfers (got {len(smoothers)}, {len(ess)}, {len(transfers)})")
+            err.code = 1
+            raise err
+        arr = lambda hs: ctypes.cast((ctypes.c_void_p * max(len(hs), 1))(*hs), ctypes.c_void_p)
+        n_ess = [0 if e is None else int(e.numel()) for e in ess]
+        h = ctypes.c_void_p()
+        _check(lib.ecm2_multigrid_create(L, arr([o._h.value for o in ops]), arr([s._h.value for s in smoothers]),
+                                         arr([t._h.value for t in transfers]),
+                                         arr([_dev_ptr(e).value if k else None for e, k in zip(ess, n_ess)]),
+                                         ctypes.cast((ctypes.c_int * max(len(n_ess), 1))(*n_ess), ctypes.c_void_p),
+                                         int(pre), int(post), ctypes.byref(h)))
+        self._h = h
+        self._keep = (list(ops), list(smoothers), list(transfers))  # alive while the cycle exists
+        self.size = ops[-1].size
+        self.set_coarse_pcg(coarse_pcg)
+
+    def set_coarse_pcg(self, coarse_pcg):
+        rel_tol, max_iter = (0.0, 0) if coarse_pcg is None else coarse_pcg
+        _check(_par_lib().ecm2_multigrid_set_coarse_pcg(self._h, float(rel_tol), int(max_iter)))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.ecm2_multigrid_destroy(self._h)
+            self._h = None
+
+    def Mult(self, x, y, stream=None):
+        """y = one V-cycle on x (MultigridBase::Mult); x, y distinct CUDA vectors of the finest size."""
+        _check_field(self, x, self.size)
+        _check_field(self, y, self.size)
+        _check(_par_lib().ecm2_multigrid_mult(self._h, _dev_ptr(x), _dev_ptr(y), _stream(stream)))
 
 
 def power_method(op, v0, ess=None, diag_of=None, num_steps=10, tol=1e-8, stream=None):

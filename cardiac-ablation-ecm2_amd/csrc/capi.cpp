@@ -10,6 +10,7 @@
 #include "par_form.hpp"
 #include "partition.hpp"
 #include "solvers.hpp"
+#include "transfer.hpp"
 
 #include <cstring>
 #include <memory>
@@ -42,6 +43,14 @@ struct ecm2_operator
 struct ecm2_smoother
 {
    std::unique_ptr<ecm2::ChebyshevSmoother> sm;
+};
+struct ecm2_transfer
+{
+   std::unique_ptr<ecm2::PTransfer> t;
+};
+struct ecm2_multigrid
+{
+   std::unique_ptr<ecm2::Multigrid> mg;
 };
 struct ecm2_linear_form
 {
@@ -1236,6 +1245,103 @@ int ecm2_ode_step_prec(int type, ecm2_operator *T, ecm2_operator *K, const doubl
       if (solves) { *solves = st.solves; }
       if (converged) { *converged = st.converged ? 1 : 0; }
       if (iterations) { *iterations = st.iterations; }
+   });
+}
+
+// ---- TensorProductPRefinementTransferOperator (fem/transfer.cpp:2223-2592) ----
+int ecm2_transfer_create(int ne, int order_lo, int ndofs_lo, const int *gather_lo, int order_hi, int ndofs_hi,
+                         const int *gather_hi, ecm2_transfer **out)
+{
+   return guard([&] {
+      NEED(out);
+      *out = nullptr;
+      *out = new ecm2_transfer{std::unique_ptr<ecm2::PTransfer>(
+         new ecm2::PTransfer(ne, order_lo, ndofs_lo, gather_lo, order_hi, ndofs_hi, gather_hi))};
+   });
+}
+
+int ecm2_transfer_mult(ecm2_transfer *t, const double *x_lo, double *y_hi, void *stream)
+{
+   return guard([&] { NEED(t); NEED(x_lo); NEED(y_hi); t->t->mult(x_lo, y_hi, S(stream)); });
+}
+
+int ecm2_transfer_mult_transpose(ecm2_transfer *t, const double *x_hi, double *y_lo, void *stream)
+{
+   return guard([&] { NEED(t); NEED(x_hi); NEED(y_lo); t->t->mult_transpose(x_hi, y_lo, S(stream)); });
+}
+
+int ecm2_transfer_info(const ecm2_transfer *t, int *ne, int *order_lo, int *order_hi, int *ndofs_lo, int *ndofs_hi,
+                       long *plan_bytes)
+{
+   return guard([&] {
+      NEED(t);
+      if (ne) { *ne = t->t->ne(); }
+      if (order_lo) { *order_lo = t->t->order_lo(); }
+      if (order_hi) { *order_hi = t->t->order_hi(); }
+      if (ndofs_lo) { *ndofs_lo = t->t->width(); }
+      if (ndofs_hi) { *ndofs_hi = t->t->height(); }
+      if (plan_bytes) { *plan_bytes = (long)t->t->plan_bytes(); }
+   });
+}
+
+void ecm2_transfer_destroy(ecm2_transfer *t) { delete t; }
+
+// ---- Multigrid (fem/multigrid.cpp:106-232, :296-309) and CGSolver with the cycle as its preconditioner ----
+int ecm2_multigrid_create(int nlevels, ecm2_operator *const *ops, ecm2_smoother *const *smoothers,
+                          ecm2_transfer *const *transfers, const int *const *ess, const int *n_ess, int pre, int post,
+                          ecm2_multigrid **out)
+{
+   return guard([&] {
+      NEED(out);
+      *out = nullptr;
+      ECM2_VERIFY(nlevels >= 1, ecm2::ERR_ARG, "multigrid: " << nlevels << " levels");
+      NEED(ops); NEED(smoothers);
+      ECM2_VERIFY(nlevels == 1 || transfers, ecm2::ERR_ARG, "null argument: transfers");
+      std::vector<ecm2::LinOp *> o;
+      std::vector<ecm2::ChebyshevSmoother *> sm;
+      std::vector<const ecm2::PTransfer *> tr;
+      std::vector<const int *> e;
+      std::vector<int> ne;
+      for (int k = 0; k < nlevels; k++)
+      {
+         NEED(ops[k]); NEED(smoothers[k]);
+         o.push_back(ops[k]->op.get());
+         sm.push_back(smoothers[k]->sm.get());
+         ne.push_back(n_ess ? n_ess[k] : 0);
+         e.push_back(ess && ne.back() ? ess[k] : nullptr);
+         if (k + 1 < nlevels)
+         {
+            NEED(transfers[k]);
+            tr.push_back(transfers[k]->t.get());
+         }
+      }
+      *out = new ecm2_multigrid{std::unique_ptr<ecm2::Multigrid>(new ecm2::Multigrid(o, sm, tr, e, ne, pre, post, nullptr))};
+   });
+}
+
+int ecm2_multigrid_set_coarse_pcg(ecm2_multigrid *mg, double rel_tol, int max_iter)
+{
+   return guard([&] { NEED(mg); mg->mg->set_coarse_pcg(rel_tol, max_iter); });
+}
+
+int ecm2_multigrid_mult(ecm2_multigrid *mg, const double *x, double *y, void *stream)
+{
+   return guard([&] { NEED(mg); NEED(x); NEED(y); mg->mg->mult(x, y, S(stream)); });
+}
+
+void ecm2_multigrid_destroy(ecm2_multigrid *mg) { delete mg; }
+
+int ecm2_operator_pcg_mg(ecm2_operator *A, ecm2_multigrid *mg, const int *ess, int n_ess, const double *b, double *x,
+                         double rel_tol, double abs_tol, int max_iter, int *iterations, double *final_norm, void *stream)
+{
+   return guard([&] {
+      NEED(A); NEED(mg); NEED(b); NEED(x);
+      g_pcg_converged = 0;
+      ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
+      const ecm2::PCGResult r = ecm2::pcg_solve_mg(*A->op, *mg->mg, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, S(stream));
+      if (iterations) { *iterations = r.iterations; }
+      if (final_norm) { *final_norm = r.final_norm; }
+      g_pcg_converged = r.converged ? 1 : 0;
    });
 }
 

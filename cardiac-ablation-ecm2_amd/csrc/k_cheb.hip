@@ -24,21 +24,6 @@ using kern::LoopCtl;
 
 constexpr int kBlocks = kern::kDotPartials;
 
-// one thread's pairs i = t, t + stride, ... < n / 2; the thread stride - 1 also takes entry n - 1 of an odd n
-struct Sweep
-{
-   long n2, stride, t;
-   bool tail;
-   __device__ explicit Sweep(int n)
-      : n2(n / 2), stride((long)gridDim.x * blockDim.x), t((long)blockIdx.x * blockDim.x + threadIdx.x),
-        tail((n & 1) && t == stride - 1)
-   {
-   }
-};
-
-__device__ inline const v2d *as2(const double *p) { return reinterpret_cast<const v2d *>(p); }
-__device__ inline v2d *as2(double *p) { return reinterpret_cast<v2d *>(p); }
-
 // t = dinv .* x (stored unless t is null: the only term of order 1), y = c0 t
 __global__ void __launch_bounds__(256)
 k_cheb_first(int n, const double *__restrict__ dinv, const double *__restrict__ x, double c0, double *__restrict__ t,

@@ -3,7 +3,8 @@
 // line / brick p >= 3 apply and the sum-factorised diagonal; k_misc.hip: workgroup-per-element
 // apply, restriction, vector and solver kernels; k_lform.hip: the linear form's element vectors;
 // k_bdr.hip: the boundary-face terms; k_conv.hip: the convection term; k_bicgstab.hip: the BiCGSTAB loop's
-// vector passes).
+// vector passes; k_cheb.hip: the Chebyshev smoother's; k_mg.hip: the multigrid cycle's; k_transfer.hip: the
+// p-refinement transfer operator, declared in transfer.hpp).
 //
 // Quadrature-data layouts (the qdata a PA form owns):
 //  * BLOCKED (fused thread-per-element kernel): elements in blocks of 64 (one
@@ -748,6 +749,15 @@ void cheb_power_pass(int n, const double *dinv, const double *h, const double *v
                      hipStream_t s);
 void cheb_scale(int n, const double *norm, double *v, hipStream_t s);
 void cheb_fill_hash(int n, double *v, hipStream_t s);
+
+// ---- vector kernels of the multigrid cycle and the PCG it preconditions (k_mg.hip) ----
+// MultigridBase::SmoothingStep / Cycle (fem/multigrid.cpp:147-232): r = x - h (h = A~ y) in one pass; y += z.
+// CGSolver's residual update alone (linalg/solvers.cpp:930-947): alpha = nom/den (-> *alpha), r -= alpha ap.
+// All vectors 16-byte aligned.
+void mg_residual(int n, const double *x, const double *h, double *r, hipStream_t s);
+void mg_add(int n, const double *z, double *y, hipStream_t s);
+void mg_pcg_step_r(int n, const double *nom, const double *den, const double *ap, double *r, double *alpha, hipStream_t s,
+                   const LoopCtl *ctl);
 } // namespace kern
 
 } // namespace ecm2

@@ -2,6 +2,7 @@
 #include "solvers.hpp"
 #include "bicgstab_stop.hpp"
 #include "cheb_coeffs.hpp"
+#include "transfer.hpp"
 
 #include <thread>
 
@@ -140,6 +141,14 @@ public:
          if (spin > 256) { std::this_thread::yield(); }
       }
    }
+   // Has the loop stopped at all, a stop in the tail of the last enqueued iteration included?  Synchronises the
+   // stream: for a caller whose next step synchronises anyway (pcg_solve_mg before a cycle with a coarse PCG).
+   bool stopped_after_sync(hipStream_t s)
+   {
+      ECM2_HIP(hipStreamSynchronize(s));
+      const volatile kern::LoopCtl *m = mirror_;
+      return m->done != 0;
+   }
    // after the loop's last kernel: the stream synchronised, then done, iters and final
    kern::LoopCtl finish(hipStream_t s)
    {
@@ -202,14 +211,26 @@ struct SolverWork
    }
 };
 
+// One workspace (and so one LoopDriver) per host thread, device and nesting depth: a solve that runs inside
+// another solve's loop -- the multigrid cycle's coarse PCG inside pcg_solve_mg -- is one level deeper and touches
+// neither the outer solve's vectors nor its loop state.  Depth 0 is every solve that is not nested.
+thread_local int g_solver_depth = 0;
+struct NestedSolve
+{
+   NestedSolve() { g_solver_depth++; }
+   ~NestedSolve() { g_solver_depth--; }
+};
+
 SolverWork &solver_work()
 {
-   static thread_local std::vector<std::unique_ptr<SolverWork>> per_device;
+   static thread_local std::vector<std::vector<std::unique_ptr<SolverWork>>> per_device;
    int dev = 0;
    ECM2_HIP(hipGetDevice(&dev));
    if ((int)per_device.size() <= dev) { per_device.resize(dev + 1); }
-   if (!per_device[dev]) { per_device[dev].reset(new SolverWork()); }
-   return *per_device[dev];
+   std::vector<std::unique_ptr<SolverWork>> &by_depth = per_device[dev];
+   if ((int)by_depth.size() <= g_solver_depth) { by_depth.resize(g_solver_depth + 1); }
+   if (!by_depth[g_solver_depth]) { by_depth[g_solver_depth].reset(new SolverWork()); }
+   return *by_depth[g_solver_depth];
 }
 
 // ConstrainedOperator::ConstrainedMult, DIAG_ONE (operator.cpp:586-646): the input's ess entries are zeroed
@@ -687,6 +708,234 @@ PCGResult pcg_solve_prec(LinOp &A, ChebyshevSmoother &B, const int *ess, int n_e
          kern::cheb_accum(n, dinv, ap, c[k], last ? nullptr : t, z, s, last ? r : nullptr, partials, ctl);
       }
       kern::dot_final(kern::kDotPartials, partials, betanom, s, ctl, &stop);
+      if (i >= max_iter) { break; }
+      // x += alpha d, d = z + beta d
+      kern::pcg_update_xd_z(n, nom, den, betanom, x, d, z, s, ctl);
+      // ap = A d, den = (A d, d) and its test (after ++i: final_iter = i + 1 on a den == 0 stop)
+      const kern::PcgStop dstop{r0, i + 1, max_iter, ctl, w.loop.mirror(), betanom, 1};
+      cmult_den(d, ap, ctl, &dstop);
+      std::swap(nom, betanom);  // nom <- betanom
+   }
+   // the stopping iteration's x += alpha d (a betanom stop)
+   kern::pcg_finish_x(n, alpha, d, x, s, ctl);
+   const kern::LoopCtl end = w.loop.finish(s);
+   ECM2_VERIFY(end.done != kern::PCG_RUNNING, ERR_INTERNAL, "device PCG loop ended without a stop");
+   const double bn = end.final;
+   ECM2_VERIFY(end.done != kern::PCG_NONFINITE, ERR_NUMERIC,
+               "PCG: non-finite (B r, r) or (A d, d) at iteration " << end.iters << " (" << bn << ")");
+   res.final_norm = bn >= 0 ? std::sqrt(bn) : bn;
+   res.iterations = end.iters;
+   res.converged = end.done == kern::PCG_CONVERGED;
+   return res;
+}
+
+// ---------------------------------------------------------------------------------------
+// Multigrid (V-cycle over caller-supplied levels) + CGSolver(prec = the cycle)
+// ---------------------------------------------------------------------------------------
+Multigrid::Multigrid(const std::vector<LinOp *> &ops, const std::vector<ChebyshevSmoother *> &smoothers,
+                     const std::vector<const PTransfer *> &transfers, const std::vector<const int *> &ess_dev,
+                     const std::vector<int> &n_ess, int pre, int post, hipStream_t s)
+   : pre_(pre), post_(post)
+{
+   // refused before anything is allocated or enqueued
+   const size_t L = ops.size();
+   ECM2_VERIFY(L >= 1, ERR_ARG, "multigrid: at least one level is needed");
+   ECM2_VERIFY(smoothers.size() == L && ess_dev.size() == L && n_ess.size() == L && transfers.size() == L - 1, ERR_ARG,
+               "multigrid: " << L << " levels need " << L << " smoothers and essential lists and " << L - 1 << " transfers");
+   ECM2_VERIFY(pre >= 0 && post >= 0, ERR_ARG, "multigrid: negative smoothing count");
+   for (size_t k = 0; k < L; k++)
+   {
+      ECM2_VERIFY(ops[k] && smoothers[k], ERR_ARG, "multigrid: null operator or smoother at level " << k);
+      ECM2_VERIFY(!ops[k]->distributed(), ERR_UNSUPPORTED, "multigrid: distributed operators are not supported");
+      ECM2_VERIFY(!ops[k]->concatenated(), ERR_UNSUPPORTED,
+                  "multigrid: a loopback group's concatenated true vectors are not a space's L-vector (level " << k << ")");
+      ECM2_VERIFY(smoothers[k]->size() == ops[k]->size(), ERR_ARG,
+                  "multigrid: level " << k << "'s smoother has size " << smoothers[k]->size() << ", its operator "
+                                      << ops[k]->size());
+      ECM2_VERIFY(n_ess[k] >= 0 && (n_ess[k] == 0 || ess_dev[k]), ERR_ARG, "multigrid: null essential dof list at level " << k);
+      if (k + 1 < L)
+      {
+         ECM2_VERIFY(transfers[k], ERR_ARG, "multigrid: null transfer " << k);
+         ECM2_VERIFY(transfers[k]->width() == ops[k]->size() && transfers[k]->height() == ops[k + 1]->size(), ERR_ARG,
+                     "multigrid: transfer " << k << " maps " << transfers[k]->width() << " -> " << transfers[k]->height()
+                                            << ", levels " << k << " and " << k + 1 << " have sizes " << ops[k]->size()
+                                            << " and " << ops[k + 1]->size());
+      }
+   }
+   lv_.resize(L);
+   for (size_t k = 0; k < L; k++)
+   {
+      Level &l = lv_[k];
+      l.A = ops[k];
+      l.S = smoothers[k];
+      l.P = k + 1 < L ? transfers[k] : nullptr;
+      l.n = ops[k]->size();
+      l.n_ess = n_ess[k];
+      const size_t m = std::max(l.n, 1);
+      l.ess.resize(std::max(l.n_ess, 1));
+      if (l.n_ess) { ECM2_HIP(hipMemcpyAsync(l.ess.data(), ess_dev[k], sizeof(int) * l.n_ess, hipMemcpyDeviceToDevice, s)); }
+      l.saved.resize(std::max(l.n_ess, 1));
+      // the per-level vectors, allocated once; the finest level's X and Y are the caller's
+      if (k + 1 < L) { l.X.resize(m); l.Y.resize(m); }
+      if (k > 0) { l.R.resize(m); l.Z.resize(m); }
+   }
+   ECM2_HIP(hipStreamSynchronize(s));
+}
+
+void Multigrid::set_coarse_pcg(double rel_tol, int max_iter)
+{
+   ECM2_VERIFY(max_iter >= 0 && rel_tol >= 0.0, ERR_ARG, "multigrid: coarse PCG rel_tol " << rel_tol << ", max_iter " << max_iter);
+   coarse_rel_tol_ = rel_tol;
+   coarse_max_iter_ = max_iter;
+}
+
+// MultigridBase::SmoothingStep (fem/multigrid.cpp:147-177): zero: Y = S X; else R = X - A~ Y, Z = S R, Y += Z
+void Multigrid::smooth(Level &l, const double *X, double *Y, bool zero, hipStream_t s)
+{
+   if (zero) { return l.S->mult(X, Y, s); }
+   const ConstrainedMult cmult{*l.A, l.ess.data(), l.n_ess, l.saved.data(), s};
+   cmult(Y, l.Z.data());  // (Z is free here: it holds A~ Y until the residual has read it)
+   kern::mg_residual(l.n, X, l.Z.data(), l.R.data(), s);
+   l.S->mult(l.R.data(), l.Z.data(), s);
+   kern::mg_add(l.n, l.Z.data(), Y, s);
+}
+
+// MultigridBase::Cycle (fem/multigrid.cpp:179-232), V-cycle
+void Multigrid::cycle(int level, const double *X, double *Y, hipStream_t s)
+{
+   Level &l = lv_[level];
+   if (level == 0)
+   {
+      if (coarse_pcg())
+      {
+         // (b) its own workspace and loop state, one nesting level below the caller's
+         const NestedSolve nested;
+         (void)pcg_solve(*l.A, l.ess.data(), l.n_ess, X, Y, coarse_rel_tol_, 0.0, coarse_max_iter_, true, s);
+      }
+      else { smooth(l, X, Y, true, s); }  // (a) SmoothingStep(0, true, false)
+      return;
+   }
+   Level &c = lv_[level - 1];
+   // pre-smooth: the first from the zero guess
+   if (pre_ == 0 && l.n) { ECM2_HIP(hipMemsetAsync(Y, 0, sizeof(double) * l.n, s)); }
+   for (int i = 0; i < pre_; i++) { smooth(l, X, Y, i == 0, s); }
+   // the residual, restricted: X[k-1] = P~^T (X - A~ Y), P~ the prolongation without its essential rows and
+   // columns (RectangularConstrainedOperator::MultTranspose: the fine essential entries of the input zeroed, the
+   // coarse essential entries of the output zeroed); Y[k-1] = 0 is the coarse level's zero guess
+   const ConstrainedMult cmult{*l.A, l.ess.data(), l.n_ess, l.saved.data(), s};
+   cmult(Y, l.Z.data());
+   kern::mg_residual(l.n, X, l.Z.data(), l.R.data(), s);
+   if (l.n_ess) { kern::set_values(l.n_ess, l.ess.data(), 0.0, l.R.data(), s); }
+   c.P->mult_transpose(l.R.data(), c.X.data(), s);
+   if (c.n_ess) { kern::set_values(c.n_ess, c.ess.data(), 0.0, c.X.data(), s); }
+   cycle(level - 1, c.X.data(), c.Y.data(), s);
+   // prolong and add: Y += P~ Y[k-1] (the coarse essential entries of the input zeroed -- in place, Y[k-1] is
+   // not read again -- and the fine essential entries of the output)
+   if (c.n_ess) { kern::set_values(c.n_ess, c.ess.data(), 0.0, c.Y.data(), s); }
+   c.P->mult(c.Y.data(), l.Z.data(), s);
+   if (l.n_ess) { kern::set_values(l.n_ess, l.ess.data(), 0.0, l.Z.data(), s); }
+   kern::mg_add(l.n, l.Z.data(), Y, s);
+   // post-smooth with the smoother's transpose, which is the smoother
+   for (int i = 0; i < post_; i++) { smooth(l, X, Y, false, s); }
+}
+
+void Multigrid::mult(const double *x, double *y, hipStream_t s)
+{
+   ECM2_VERIFY(x && y, ERR_ARG, "multigrid: null vector");
+   ECM2_VERIFY(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0, ERR_ARG,
+               "multigrid: x and y must be 16-byte aligned (got " << (const void *)x << ", " << (const void *)y << ")");
+   ECM2_VERIFY(x != y, ERR_ARG, "multigrid: x and y must be distinct");
+   cycle(levels() - 1, x, y, s);
+}
+
+PCGResult pcg_solve_mg(LinOp &A, Multigrid &B, const int *ess, int n_ess, const double *b, double *x, double rel_tol,
+                       double abs_tol, int max_iter, hipStream_t s)
+{
+   // refused before anything is enqueued, as in pcg_solve
+   ECM2_VERIFY(((uintptr_t)x % 16) == 0, ERR_ARG, "PCG: x must be 16-byte aligned (got " << (const void *)x << ")");
+   ECM2_VERIFY(!A.distributed(), ERR_UNSUPPORTED, "PCG with a multigrid cycle: distributed operators are not supported");
+   ECM2_VERIFY(!A.concatenated(), ERR_UNSUPPORTED,
+               "PCG with a multigrid cycle: a loopback group's vectors are not in the cycle's numbering");
+   const int n = A.size();
+   ECM2_VERIFY(B.size() == n, ERR_ARG, "PCG: the multigrid's finest level has size " << B.size() << ", the operator " << n);
+   PCGResult res;
+   const int nen = A.energy_parts();  // (A d, d) folded into the Mult where the operator can, as in pcg_solve
+   SolverWork &w = solver_work();
+   w.ensure(n, n_ess, false, false, std::max({kern::kDotPartials, kern::step_parts(n), nen + kern::ess_parts(n_ess)}), true);
+   double *r = w.r.data(), *d = w.p.data(), *ap = w.ap.data(), *z = w.z.data();
+   double *partials = w.partials.data();
+   double *nom = w.scal.data(), *den = w.scal.data() + 1, *betanom = w.scal.data() + 2, *alpha = w.scal.data() + 3;
+   auto readback = [&]() {
+      ECM2_HIP(hipStreamSynchronize(s));
+      return *(volatile double *)w.hs;
+   };
+   const ConstrainedMult cmult{A, ess, n_ess, w.saved.data(), s};
+   auto cmult_den = [&](double *in, double *out, const kern::LoopCtl *ctl, const kern::PcgStop *stop) {
+      if (nen > 0)
+      {
+         cmult(in, out, partials);
+         kern::dot_final(nen + kern::ess_parts(n_ess), partials, den, s, ctl, stop, ctl ? nullptr : w.hs_dev);
+      }
+      else
+      {
+         cmult(in, out);
+         kern::dot(n, in, out, partials, den, s, ctl ? nullptr : w.hs_dev, ctl, stop);
+      }
+   };
+   if (n) { ECM2_HIP(hipMemcpyAsync(r, b, sizeof(double) * n, hipMemcpyDeviceToDevice, s)); }
+   if (n) { ECM2_HIP(hipMemsetAsync(x, 0, sizeof(double) * n, s)); }
+   // z = B r, d = z, nom = (d, r) (solvers.cpp:893-903)
+   B.mult(r, z, s);
+   if (n) { ECM2_HIP(hipMemcpyAsync(d, z, sizeof(double) * n, hipMemcpyDeviceToDevice, s)); }
+   kern::dot(n, d, r, partials, nom, s, w.hs_dev);
+   const double nom0 = readback();
+   ECM2_VERIFY(std::isfinite(nom0), ERR_NUMERIC, "PCG: nom = " << nom0);
+   res.initial_norm = nom0 >= 0 ? std::sqrt(nom0) : nom0;
+   res.final_norm = res.initial_norm;
+   if (nom0 < 0.0)
+   {
+      // the cycle is not positive definite: not converged, final_norm = nom (:905-917)
+      res.initial_norm = res.final_norm = nom0;
+      return res;
+   }
+   const double r0 = std::max(nom0 * rel_tol * rel_tol, abs_tol * abs_tol);
+   if (nom0 <= r0)
+   {
+      res.converged = true;
+      return res;
+   }
+   w.loop.reset(s);
+   cmult_den(d, ap, nullptr, nullptr);
+   const double den0 = readback();
+   ECM2_VERIFY(std::isfinite(den0), ERR_NUMERIC, "PCG: den = " << den0);
+   if (den0 == 0.0) { return res; }
+   // CGSolver's loop driven by the device exactly as pcg_solve's (see there).  The order of events around a stop:
+   //  1. stopped_by(i - 1) answers for the stops found up to the betanom test of i - 1.  A stop the device finds
+   //     after that, in the (A d, d) test of i - 1's tail, carries iters = i and may not be visible yet, so the
+   //     host may enqueue iteration i once more; its own kernels (mg_pcg_step_r, dot, pcg_update_xd_z, the Mult's
+   //     test) return at once.
+   //  2. The cycle's kernels are not keyed on the loop state.  With the smoother as the coarse solve (a) a cycle
+   //     enqueued in such an iteration runs on the unchanged r and writes z and its own vectors, which nothing
+   //     after the loop reads (pcg_finish_x reads alpha, d and x): the result cannot change, and the cycle has no
+   //     host-side check that could raise.
+   //  3. With a coarse PCG (b) the cycle synchronises the stream and its inner solve reads back and verifies its
+   //     own scalars.  Before such a cycle the host therefore synchronises and looks at the outer loop's state
+   //     itself: after any stop, the tail's included, no further cycle is enqueued, so an inner solve can neither
+   //     run on a stopped loop's vectors nor raise over the outer loop's own stop, which finish() reports below.
+   //     While the outer loop runs, the inner solve works one nesting level down (its own SolverWork and
+   //     LoopDriver) and ends with the stream synchronised.
+   kern::LoopCtl *ctl = w.loop.ctl();
+   for (int i = 1;; i++)
+   {
+      if (i > 1 && w.loop.stopped_by(i - 1, s, "PCG")) { break; }
+      if (i > 1 && B.coarse_pcg() && w.loop.stopped_after_sync(s)) { break; }
+      const kern::PcgStop stop{r0, i, max_iter, ctl, w.loop.mirror()};
+      // r -= alpha A d
+      kern::mg_pcg_step_r(n, nom, den, ap, r, alpha, s, ctl);
+      // z = B r: one cycle
+      B.mult(r, z, s);
+      // betanom = (r, z) and its test
+      kern::dot(n, r, z, partials, betanom, s, nullptr, ctl, &stop);
       if (i >= max_iter) { break; }
       // x += alpha d, d = z + beta d
       kern::pcg_update_xd_z(n, nom, den, betanom, x, d, z, s, ctl);

@@ -11,6 +11,8 @@
 //   OperatorJacobiSmoother (PA diagonal)       linalg/solvers.hpp:421, bilinearform_ext.cpp:370-454
 //   OperatorChebyshevSmoother                  linalg/solvers.hpp:498-586, solvers.cpp:455-658
 //   PowerMethod::EstimateLargestEigenvalue     linalg/operator.cpp:871-928
+//   Multigrid / MultigridBase (V-cycle)        fem/multigrid.cpp:106-232
+//   GeometricMultigrid's constrained transfers fem/multigrid.cpp:296-309
 //   parallel dot (MPI_Allreduce)               linalg/hypre / InnerProduct(comm, ...)
 //   BackwardEuler / SDIRK23 / SDIRK33 / ImplicitMidpoint / SDIRK34 ::Step
 //                                              linalg/ode.cpp:682-859, selection :77-91
@@ -39,6 +41,9 @@ public:
    virtual void sum_scalars(double *dev, int n, hipStream_t s) { (void)dev; (void)n; (void)s; }
    // true when sum_scalars communicates (a locally reduced scalar is not yet global)
    virtual bool distributed() const { return false; }
+   // true when the vectors are the concatenated true vectors of a loopback group's members and not one space's
+   // L-vector: what acts in a space's numbering (the multigrid's transfers and essential lists) refuses it
+   virtual bool concatenated() const { return false; }
    // The Mult with its energy x^T A x folded in as energy_parts() partials (PAForm::mult_energy),
    // or 0 when this operator does not fold it
    virtual int energy_parts() const { return 0; }
@@ -84,6 +89,7 @@ class GroupOp : public LinOp
 public:
    explicit GroupOp(std::vector<ParPAForm *> forms);
    int size() const override { return n_; }
+   bool concatenated() const override { return true; }
    void mult(const double *x, double *y, hipStream_t s) override;
    void diagonal(double *d, hipStream_t s) override;
    int offset(int r) const { return off_[r]; }
@@ -212,6 +218,65 @@ private:
 // (r, z).  B must be of A's size (ERR_ARG); x 16-byte aligned (ERR_ARG); distributed operators: ERR_UNSUPPORTED.
 PCGResult pcg_solve_prec(LinOp &A, ChebyshevSmoother &B, const int *ess_dev, int n_ess, const double *b, double *x,
                          double rel_tol, double abs_tol, int max_iter, hipStream_t s);
+
+// Multigrid / MultigridBase (fem/multigrid.cpp:106-232: Mult, SmoothingStep, Cycle), V-cycle only, over levels 0
+// (coarsest) .. L - 1 that the caller supplies: each level's operator, its ChebyshevSmoother (built by the caller
+// on that level's operator and essential list), its essential list (device, copied) and the transfer k -> k + 1
+// (a PTransfer; Multigrid takes them as objects so that another kind of transfer can be added).  The essential
+// rows and columns of the prolongations are removed as GeometricMultigrid does (fem/multigrid.cpp:296-309,
+// RectangularConstrainedOperator): the coarse essential entries of the input and the fine essential entries of
+// the output are zero, and likewise for the transpose.
+// mult(x, y): one cycle from a zero guess (iterative_mode is not used), the reference's operations per entry:
+//   the first pre-smoothing Y = S X; every other smoothing R = X - A~ Y, Y += S R (A~ the DIAG_ONE constrained
+//   Mult; the post-smoothing's S^T is S: OperatorChebyshevSmoother::MultTranspose calls Mult); the residual
+//   restricted into X[k-1]; the coarse correction prolonged and added.
+// The coarsest level: (a) its smoother applied once (Multigrid's smoother at level 0), or (b) after
+// set_coarse_pcg(rel_tol, max_iter > 0) a constrained Jacobi-PCG from a zero guess (ex26: sqrt(1e-4), 200), which
+// synchronises the stream; with (b) the cycle is not a symmetric operator.
+// Sizes that do not chain (transfer k's width / height against levels k / k + 1, a smoother's size against its
+// level): ERR_ARG; no level: ERR_ARG; distributed operators, and a loopback group (whose concatenated true vectors
+// are not in the numbering of the transfers and essential lists): ERR_UNSUPPORTED.  x, y: device vectors of the finest
+// size, 16-byte aligned and distinct (ERR_ARG).  Operators, smoothers and transfers must outlive it.  Two cycles
+// are bitwise equal.
+class PTransfer;
+class Multigrid
+{
+public:
+   Multigrid(const std::vector<LinOp *> &ops, const std::vector<ChebyshevSmoother *> &smoothers,
+             const std::vector<const PTransfer *> &transfers, const std::vector<const int *> &ess_dev,
+             const std::vector<int> &n_ess, int pre, int post, hipStream_t s);
+   int levels() const { return (int)lv_.size(); }
+   int size() const { return lv_.back().n; }
+   void set_coarse_pcg(double rel_tol, int max_iter);
+   // the coarse solve synchronises the stream and may throw ERR_NUMERIC (what pcg_solve_mg orders its events by)
+   bool coarse_pcg() const { return coarse_max_iter_ > 0; }
+   void mult(const double *x, double *y, hipStream_t s);
+
+private:
+   struct Level
+   {
+      LinOp *A = nullptr;
+      ChebyshevSmoother *S = nullptr;
+      const PTransfer *P = nullptr;  // this level -> the next finer one (null on the finest)
+      int n = 0, n_ess = 0;
+      DeviceArray<int> ess;
+      DeviceArray<double> X, Y, R, Z, saved;
+   };
+   void smooth(Level &l, const double *X, double *Y, bool zero, hipStream_t s);
+   void cycle(int level, const double *X, double *Y, hipStream_t s);
+   std::vector<Level> lv_;
+   int pre_, post_;
+   double coarse_rel_tol_ = 0.0;
+   int coarse_max_iter_ = 0;
+};
+
+// CGSolver::Mult (linalg/solvers.cpp:869-1004) with prec = the cycle on the constrained A, x overwritten:
+// pcg_solve_prec's loop (the same device-driven stops, the same folded (A d, d), the same deferred x += alpha d,
+// the same results and read-backs) with z = B r computed by the cycle between the pass that updates r and the pass
+// that sums (r, z).  B must be of A's size (ERR_ARG); x 16-byte aligned (ERR_ARG); distributed operators and a
+// loopback group as A: ERR_UNSUPPORTED.
+PCGResult pcg_solve_mg(LinOp &A, Multigrid &B, const int *ess_dev, int n_ess, const double *b, double *x, double rel_tol,
+                       double abs_tol, int max_iter, hipStream_t s);
 
 // ODESolver::SelectImplicit numbering (ode.cpp:77-91): 21 BackwardEuler, 22 SDIRK23(L-stable),
 // 23 SDIRK33, 32 ImplicitMidpoint, 33 SDIRK23 (A-stable, order 3), 34 SDIRK34.

@@ -542,6 +542,60 @@ int ecm2_operator_pcg_prec(ecm2_operator *A, ecm2_smoother *sm, const int *ess, 
 int ecm2_ode_step_prec(int type, ecm2_operator *T, ecm2_operator *K, const double *b /* NULL */, ecm2_smoother *sm,
                        double dt, double *u, const int *ess, int n_ess, double rel_tol, int max_iter, int *solves,
                        int *iterations, int *converged, void *stream);
+
+/* ------------------------------------------------------------------------ */
+/* p-multigrid: TensorProductPRefinementTransferOperator (fem/transfer.cpp:   */
+/* 2223-2592), Multigrid's V-cycle (fem/multigrid.cpp:106-232) and            */
+/* CGSolver::Mult (linalg/solvers.cpp:869-1004) with the cycle as prec        */
+/* ------------------------------------------------------------------------ */
+/* TensorProductPRefinementTransferOperator(lFESpace, hFESpace) (fem/transfer.cpp:2223-2287) between two H1 spaces
+ * of orders order_lo < order_hi on the same ne elements in the same element order, each given by its gather map
+ * (host int [ne][(order + 1)^3], lexicographic local dofs, as ecm2_pa_form_create's); nothing else about the
+ * spaces is read.  The mask (ElementRestriction::BooleanMask, fem/restriction.cpp:248-283) is built here as owner
+ * bits.  order_lo >= order_hi: ECM2_ERR_ARG; an order outside 1..4: ECM2_ERR_UNSUPPORTED; a map entry >= ndofs or
+ * a fine dof that no element holds: ECM2_ERR_ARG; a negative (signed) entry: ECM2_ERR_UNSUPPORTED. */
+typedef struct ecm2_transfer ecm2_transfer;
+int ecm2_transfer_create(int ne, int order_lo, int ndofs_lo, const int *gather_lo, int order_hi, int ndofs_hi,
+                         const int *gather_hi, ecm2_transfer **out);
+/* Mult (fem/transfer.cpp:2542-2566, Prolongation3D :2338-2423): y_hi = P x_lo, device L-vectors of ndofs_lo and
+ * ndofs_hi doubles; y_hi is overwritten, every entry once by its owner element (no zero fill, no atomics). */
+int ecm2_transfer_mult(ecm2_transfer *t, const double *x_lo, double *y_hi, void *stream);
+/* MultTranspose (fem/transfer.cpp:2568-2592, Restriction3D :2470-2539): y_lo = P^T x_hi, summed over the elements
+ * that share a coarse dof in a fixed order (no atomics); y_lo is overwritten.  Two calls are bitwise equal. */
+int ecm2_transfer_mult_transpose(ecm2_transfer *t, const double *x_hi, double *y_lo, void *stream);
+/* ne, the two orders and sizes, and the bytes of the device plan (both maps, the owner words, the coarse
+ * transposed map); any pointer may be NULL. */
+int ecm2_transfer_info(const ecm2_transfer *t, int *ne, int *order_lo, int *order_hi, int *ndofs_lo, int *ndofs_hi,
+                       long *plan_bytes);
+void ecm2_transfer_destroy(ecm2_transfer *t);
+/* Multigrid(operators, smoothers, prolongations) (fem/multigrid.cpp:234-244) with the essential rows and columns of
+ * the prolongations removed as GeometricMultigrid does (fem/multigrid.cpp:296-309): levels 0 (coarsest) ..
+ * nlevels - 1; ops[k], smoothers[k] (built by the caller on ops[k] with ess[k]) and ess[k] (device int
+ * [n_ess[k]], copied) per level, transfers[k] from level k to k + 1 (nlevels - 1 of them); pre and post smoothing
+ * counts (the reference's defaults 1, 1).  V-cycle.  Sizes that do not chain or nlevels < 1: ECM2_ERR_ARG;
+ * operators whose dots need communication, and a loopback group (ecm2_operator_from_par_group: its vectors are the
+ * members' concatenated true vectors, not the L-vectors the transfers and essential lists number):
+ * ECM2_ERR_UNSUPPORTED.  Every array holds nlevels entries (transfers: nlevels - 1); everything passed in must
+ * outlive it. */
+typedef struct ecm2_multigrid ecm2_multigrid;
+int ecm2_multigrid_create(int nlevels, ecm2_operator *const *ops, ecm2_smoother *const *smoothers,
+                          ecm2_transfer *const *transfers, const int *const *ess, const int *n_ess, int pre, int post,
+                          ecm2_multigrid **out);
+/* The coarsest level's solve: max_iter > 0: a constrained Jacobi-PCG from a zero guess with rel_tol and max_iter
+ * (examples/ex26.cpp: sqrt(1e-4), 200); max_iter = 0: the level's smoother applied once (Multigrid's smoother at
+ * level 0, fem/multigrid.cpp:179-186), the default. */
+int ecm2_multigrid_set_coarse_pcg(ecm2_multigrid *mg, double rel_tol, int max_iter);
+/* MultigridBase::Mult (fem/multigrid.cpp:106-145): y = one V-cycle (Cycle, SmoothingStep, :147-232) on x from a
+ * zero guess; x, y distinct device vectors of the finest level's size, 16-byte aligned (ECM2_ERR_ARG otherwise).
+ * Two calls are bitwise equal. */
+int ecm2_multigrid_mult(ecm2_multigrid *mg, const double *x, double *y, void *stream);
+void ecm2_multigrid_destroy(ecm2_multigrid *mg);
+/* ecm2_operator_pcg_prec with prec = the cycle (CGSolver::Mult, solvers.cpp:869-1004; the finest level of A's
+ * size, ECM2_ERR_ARG otherwise; A a loopback group: ECM2_ERR_UNSUPPORTED): the same stops, read-backs and results
+ * as there. */
+int ecm2_operator_pcg_mg(ecm2_operator *A, ecm2_multigrid *mg, const int *ess, int n_ess, const double *b, double *x,
+                         double rel_tol, double abs_tol, int max_iter, int *iterations, double *final_norm,
+                         void *stream);
 void ecm2_operator_destroy(ecm2_operator *op);
 
 /* ------------------------------------------------------------------------ */
