@@ -63,6 +63,20 @@ thread_local std::string g_last_error;
 thread_local int g_pcg_converged = 0;  // IterativeSolver::GetConverged() of the thread's last PCG
 thread_local int g_bicgstab_converged = 0;  // ... of the thread's last BiCGSTAB
 
+// a solve's and a step's results into the caller's (optional) outputs; `flag`: the thread's converged flag
+void report(const ecm2::PCGResult &r, int *iterations, double *final_norm, int &flag)
+{
+   if (iterations) { *iterations = r.iterations; }
+   if (final_norm) { *final_norm = r.final_norm; }
+   flag = r.converged ? 1 : 0;
+}
+void report(const ecm2::StepStats &st, int *solves, int *iterations, int *converged)
+{
+   if (solves) { *solves = st.solves; }
+   if (converged) { *converged = st.converged ? 1 : 0; }
+   if (iterations) { *iterations = st.iterations; }
+}
+
 template <typename F>
 int guard(F &&fn)
 {
@@ -717,9 +731,7 @@ int ecm2_pcg_solve(ecm2_pa_form *f, const int *ess, int n_ess, const double *b, 
       ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
       const ecm2::PCGResult r = ecm2::pcg_solve(*f->f, ess, n_ess, b, x, rel_tol, abs_tol,
                                                 max_iter, jacobi != 0, S(stream));
-      if (iterations) { *iterations = r.iterations; }
-      if (final_norm) { *final_norm = r.final_norm; }
-      g_pcg_converged = r.converged ? 1 : 0;
+      report(r, iterations, final_norm, g_pcg_converged);
    });
 }
 
@@ -1086,9 +1098,7 @@ int ecm2_operator_pcg(ecm2_operator *op, const int *ess, int n_ess, const double
       ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
       const ecm2::PCGResult r = ecm2::pcg_solve(*op->op, ess, n_ess, b, x, rel_tol, abs_tol, max_iter,
                                                 jacobi != 0, S(stream));
-      if (iterations) { *iterations = r.iterations; }
-      if (final_norm) { *final_norm = r.final_norm; }
-      g_pcg_converged = r.converged ? 1 : 0;
+      report(r, iterations, final_norm, g_pcg_converged);
    });
 }
 
@@ -1107,9 +1117,7 @@ int ecm2_ode_step_source(int type, ecm2_operator *T, ecm2_operator *K, const dou
       ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
       const ecm2::StepStats st = ecm2::ode_step(type, *T->op, *K->op, dt, u, ess, n_ess, rel_tol, max_iter,
                                                 jacobi != 0, S(stream), b);
-      if (solves) { *solves = st.solves; }
-      if (converged) { *converged = st.converged ? 1 : 0; }
-      if (iterations) { *iterations = st.iterations; }
+      report(st, solves, iterations, converged);
    });
 }
 
@@ -1134,9 +1142,7 @@ int ecm2_operator_bicgstab(ecm2_operator *A, ecm2_operator *jacobi_of, const int
       ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
       const ecm2::PCGResult r = ecm2::bicgstab_solve(*A->op, jacobi_of ? jacobi_of->op.get() : nullptr, ess, n_ess, b, x,
                                                      rel_tol, abs_tol, max_iter, S(stream));
-      if (iterations) { *iterations = r.iterations; }
-      if (final_norm) { *final_norm = r.final_norm; }
-      g_bicgstab_converged = r.converged ? 1 : 0;
+      report(r, iterations, final_norm, g_bicgstab_converged);
    });
 }
 
@@ -1150,9 +1156,7 @@ int ecm2_ode_step_bicgstab(int type, ecm2_operator *T, ecm2_operator *jacobi_of,
       const ecm2::StepStats st = ecm2::ode_step(type, *T->op, *K->op, dt, u, ess, n_ess, rel_tol, max_iter, false,
                                                 S(stream), b, ecm2::STAGE_BICGSTAB,
                                                 jacobi_of ? jacobi_of->op.get() : nullptr);
-      if (solves) { *solves = st.solves; }
-      if (converged) { *converged = st.converged ? 1 : 0; }
-      if (iterations) { *iterations = st.iterations; }
+      report(st, solves, iterations, converged);
    });
 }
 
@@ -1227,9 +1231,7 @@ int ecm2_operator_pcg_prec(ecm2_operator *A, ecm2_smoother *sm, const int *ess, 
       ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
       const ecm2::PCGResult r = ecm2::pcg_solve_prec(*A->op, *sm->sm, ess, n_ess, b, x, rel_tol, abs_tol, max_iter,
                                                      S(stream));
-      if (iterations) { *iterations = r.iterations; }
-      if (final_norm) { *final_norm = r.final_norm; }
-      g_pcg_converged = r.converged ? 1 : 0;
+      report(r, iterations, final_norm, g_pcg_converged);
    });
 }
 
@@ -1242,9 +1244,7 @@ int ecm2_ode_step_prec(int type, ecm2_operator *T, ecm2_operator *K, const doubl
       ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
       const ecm2::StepStats st = ecm2::ode_step(type, *T->op, *K->op, dt, u, ess, n_ess, rel_tol, max_iter, false,
                                                 S(stream), b, ecm2::STAGE_PCG, nullptr, sm->sm.get());
-      if (solves) { *solves = st.solves; }
-      if (converged) { *converged = st.converged ? 1 : 0; }
-      if (iterations) { *iterations = st.iterations; }
+      report(st, solves, iterations, converged);
    });
 }
 
@@ -1339,9 +1339,7 @@ int ecm2_operator_pcg_mg(ecm2_operator *A, ecm2_multigrid *mg, const int *ess, i
       g_pcg_converged = 0;
       ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
       const ecm2::PCGResult r = ecm2::pcg_solve_mg(*A->op, *mg->mg, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, S(stream));
-      if (iterations) { *iterations = r.iterations; }
-      if (final_norm) { *final_norm = r.final_norm; }
-      g_pcg_converged = r.converged ? 1 : 0;
+      report(r, iterations, final_norm, g_pcg_converged);
    });
 }
 

@@ -142,7 +142,7 @@ public:
       }
    }
    // Has the loop stopped at all, a stop in the tail of the last enqueued iteration included?  Synchronises the
-   // stream: for a caller whose next step synchronises anyway (pcg_solve_mg before a cycle with a coarse PCG).
+   // stream: for a caller whose next step synchronises anyway (pcg_loop before a cycle with a coarse PCG).
    bool stopped_after_sync(hipStream_t s)
    {
       ECM2_HIP(hipStreamSynchronize(s));
@@ -263,19 +263,59 @@ void jacobi_dinv(LinOp &D, const int *ess, int n_ess, double *scratch, double *d
 } // namespace
 
 // ---------------------------------------------------------------------------------------
-// ConstrainedOperator + CGSolver + OperatorJacobiSmoother
+// ConstrainedOperator + CGSolver, prec = none | OperatorJacobiSmoother | OperatorChebyshevSmoother | Multigrid
 // ---------------------------------------------------------------------------------------
-
-PCGResult pcg_solve(LinOp &A, const int *ess, int n_ess, const double *b, double *x, double rel_tol,
-                    double abs_tol, int max_iter, bool jacobi, hipStream_t s)
+namespace
 {
-   // k_pcg_update_xd / k_pcg_step_r / k_pcg_finish_x read and write the caller's x two entries at a
-   // time; refused here, before anything is enqueued (the work vectors are allocations of their own)
+// One solve's operator, vectors and device scalars, as the loop and its preconditioner see them.
+struct PcgState
+{
+   LinOp &A;
+   const int *ess;
+   int n_ess, n;
+   // serial: the final-dot kernel also writes the value into mapped pinned memory and runs the stopping test;
+   // distributed: the value is copied after the all-reduce, the test is a kernel of its own (pcg_check)
+   bool direct;
+   SolverWork &w;
+   hipStream_t s;
+   double *x, *r, *d, *ap, *partials;    // the caller's x; the residual, the direction, A d (SolverWork's r, p, ap)
+   double *nom, *den, *betanom, *alpha;  // device scalars; nom and betanom swap roles every iteration (no copy)
+   kern::LoopCtl *ctl;
+   void copy(double *dst, const double *src) const
+   {
+      if (n) { ECM2_HIP(hipMemcpyAsync(dst, src, sizeof(double) * n, hipMemcpyDeviceToDevice, s)); }
+   }
+};
+
+// What differs between CGSolver's preconditioners B: how z = B r enters an iteration, and which direction update
+// consumes it.  Everything else is pcg_loop.
+struct PcgPrec
+{
+   // what the solve needs from SolverWork::ensure: dinv; z and the smoother's term; room on `saved` for the
+   // essential entries of the preconditioner's own constrained Mult
+   bool jacobi = false, stored_z = false;
+   int n_ess = 0;
+   // applying it synchronises the stream and may raise (the cycle with a coarse PCG)
+   bool syncs = false;
+   virtual void setup(PcgState &) {}        // once, before r = b is enqueued
+   virtual void first(PcgState &p) = 0;     // d = B r
+   // the residual half of an iteration: r -= alpha A d, betanom = (r, B r) and its test
+   virtual void step_r(PcgState &p, const kern::PcgStop &stop) = 0;
+   virtual void update_xd(PcgState &p) = 0;  // the direction half: x += alpha d, d = B r + beta d
+
+protected:
+   ~PcgPrec() = default;
+};
+
+// CGSolver::Mult (solvers.cpp:869-1004) on the constrained A, x overwritten.
+PCGResult pcg_loop(LinOp &A, PcgPrec &B, const int *ess, int n_ess, const double *b, double *x, double rel_tol,
+                   double abs_tol, int max_iter, hipStream_t s)
+{
+   // the update passes and k_pcg_finish_x read and write the caller's x two entries at a time; refused here,
+   // before anything is allocated or enqueued (the work vectors are allocations of their own)
    ECM2_VERIFY(((uintptr_t)x % 16) == 0, ERR_ARG, "PCG: x must be 16-byte aligned (got " << (const void *)x << ")");
    const int n = A.size();
    PCGResult res;
-   // serial: the final-dot kernel also writes the value into mapped pinned memory, so the
-   // stopping test needs only a stream sync; distributed: copy after the all-reduce
    const bool direct = !A.distributed();
    // den = (A d, d) folded into the Mult where the operator can (serial snapshot forms): the
    // kernel's element energies sum_e d~_e . A_e d~_e (d~ = d with the ess entries zeroed, as the
@@ -284,120 +324,199 @@ PCGResult pcg_solve(LinOp &A, const int *ess, int n_ess, const double *b, double
    // dot_final: no pass over the two vectors (2 streams and a launch per iteration).
    const int nen = direct ? A.energy_parts() : 0;
    SolverWork &w = solver_work();
-   w.ensure(n, n_ess, jacobi, false, std::max({kern::kDotPartials, kern::step_parts(n), nen + kern::ess_parts(n_ess)}));
-   double *r = w.r.data(), *d = w.p.data(), *z = w.ap.data(), *dinv = jacobi ? w.dinv.data() : nullptr;
-   double *partials = w.partials.data();
-   // device scalars; nom and betanom swap roles every iteration (no copy); alpha of the last step
-   double *nom = w.scal.data(), *den = w.scal.data() + 1, *betanom = w.scal.data() + 2, *alpha = w.scal.data() + 3;
-   auto dot = [&](const double *a, const double *bb, double *out, const kern::LoopCtl *c = nullptr) {
-      kern::dot(n, a, bb, partials, out, s, direct && !c ? w.hs_dev : nullptr, c);
-      A.sum_scalars(out, 1, s);
-   };
+   w.ensure(n, std::max(n_ess, B.n_ess), B.jacobi, false,
+            std::max({kern::kDotPartials, kern::step_parts(n), nen + kern::ess_parts(n_ess)}), B.stored_z);
+   double *const scal = w.scal.data();
+   PcgState p{A, ess, n_ess, n, direct, w, s, x, w.r.data(), w.p.data(), w.ap.data(), w.partials.data(),
+              scal, scal + 1, scal + 2, scal + 3, w.loop.ctl()};
    auto readback = [&](const double *dv) {
       if (!direct) { ECM2_HIP(hipMemcpyAsync(w.hs, dv, sizeof(double), hipMemcpyDeviceToHost, s)); }
       ECM2_HIP(hipStreamSynchronize(s));
       return *(volatile double *)w.hs;
    };
    const ConstrainedMult cmult{A, ess, n_ess, w.saved.data(), s};
-   auto cmult_den = [&](double *in, double *out, const kern::LoopCtl *c, const kern::PcgStop *stop) {
-      cmult(in, out, partials);
-      kern::dot_final(nen + kern::ess_parts(n_ess), partials, den, s, c, stop, c ? nullptr : w.hs_dev);
+   // ap = A d, den = (A d, d); in the loop (c) with its test, before it with the value for the read-back
+   auto cmult_den = [&](const kern::LoopCtl *c, const kern::PcgStop *stop) {
+      if (nen > 0)
+      {
+         cmult(p.d, p.ap, p.partials);
+         kern::dot_final(nen + kern::ess_parts(n_ess), p.partials, p.den, s, c, stop, c ? nullptr : w.hs_dev);
+         return;
+      }
+      cmult(p.d, p.ap);
+      kern::dot(n, p.d, p.ap, p.partials, p.den, s, direct && !c ? w.hs_dev : nullptr, c, direct ? stop : nullptr);
+      if (!direct)
+      {
+         A.sum_scalars(p.den, 1, s);
+         if (stop) { kern::pcg_check(p.den, *stop, s); }
+      }
    };
-   if (jacobi) { jacobi_dinv(A, ess, n_ess, z, dinv, s); }
-   if (n) { ECM2_HIP(hipMemcpyAsync(r, b, sizeof(double) * n, hipMemcpyDeviceToDevice, s)); }
+   B.setup(p);
+   p.copy(p.r, b);
    if (n) { ECM2_HIP(hipMemsetAsync(x, 0, sizeof(double) * n, s)); }
-   if (jacobi)
-   {
-      kern::pcg_precond(n, dinv, r, z, s);
-      if (n) { ECM2_HIP(hipMemcpyAsync(d, z, sizeof(double) * n, hipMemcpyDeviceToDevice, s)); }
-   }
-   else if (n)
-   {
-      ECM2_HIP(hipMemcpyAsync(d, r, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-   }
-   dot(d, r, nom);
-   const double nom0 = readback(nom);
+   // d = B r, nom = (d, r) (solvers.cpp:893-903)
+   B.first(p);
+   kern::dot(n, p.d, p.r, p.partials, p.nom, s, direct ? w.hs_dev : nullptr);
+   if (!direct) { A.sum_scalars(p.nom, 1, s); }
+   // Every return below follows a read-back (or finish()) with nothing enqueued after it: the stream is
+   // synchronised, which is SolverWork's invariant.
+   const double nom0 = readback(p.nom);
    // CGSolver::Mult's checks before the loop (solvers.cpp:893-948)
    ECM2_VERIFY(std::isfinite(nom0), ERR_NUMERIC, "PCG: nom = " << nom0);
    res.initial_norm = nom0 >= 0 ? std::sqrt(nom0) : nom0;
    res.final_norm = res.initial_norm;
-   if (nom0 < 0.0)
+   // the preconditioner is not positive definite (a smoother whose estimate is far below the largest eigenvalue,
+   // a cycle of such smoothers): not converged, final_norm = nom (:905-917)
+   if (nom0 < 0.0) { return res; }
+   const double r0 = std::max(nom0 * rel_tol * rel_tol, abs_tol * abs_tol);
+   if (nom0 <= r0)
    {
-      // the preconditioner is not positive definite: not converged, final_norm = nom (:905-917)
-      res.initial_norm = res.final_norm = nom0;
-      ECM2_HIP(hipStreamSynchronize(s));
+      res.converged = true;
       return res;
    }
-   const double r0 = std::max(nom0 * rel_tol * rel_tol, abs_tol * abs_tol);
-   if (nom0 <= r0) { res.converged = true; }
-   else
+   // the device-driven loop's state, reset before the read-back below idles the stream
+   w.loop.reset(s);
+   cmult_den(nullptr, nullptr);
+   const double den0 = readback(p.den);
+   ECM2_VERIFY(std::isfinite(den0), ERR_NUMERIC, "PCG: den = " << den0);
+   if (den0 == 0.0) { return res; }
+   // CGSolver's loop (solvers.cpp:930-1000) driven by the device: the stopping tests run on the device after each
+   // (r, B r) and each (A d, d) (in the dot's final pass, or in a one-thread kernel after the all-reduce), and once
+   // one stops every later vector kernel of the loop returns at once.  The host enqueues iteration i as soon as the
+   // betanom test of i - 1 has run (it polls the mirror's progress mark; no host synchronisation of the stream), so
+   // the queue holds the rest of iteration i - 1 while it does, and it ends at the iteration the device stopped
+   // at: the same iteration on every rank, so the ranks issue the same collectives.  The iterates are CGSolver's
+   // (the same operations per entry, in its order; x += alpha d deferred into the next pass that reads d); at
+   // most the stopping iteration's Mult runs after the stop.  The order of events around a stop:
+   //  1. stopped_by(i - 1) answers for the stops found up to the betanom test of i - 1.  A stop the device finds
+   //     after that, in the (A d, d) test of i - 1's tail, carries iters = i and may not be visible yet, so the
+   //     host may enqueue iteration i once more; the loop's own kernels (step_r's, update_xd's, the Mult's test)
+   //     return at once.
+   //  2. A preconditioner's own kernels (the smoother's Mults, the cycle) are not keyed on the loop state.  One
+   //     that is enqueued in such an iteration runs on the unchanged r and writes z and its own vectors, which
+   //     nothing after the loop reads (pcg_finish_x reads alpha, d and x): the result cannot change, and it has no
+   //     host-side check that could raise.
+   //  3. A preconditioner that synchronises (B.syncs: the cycle with a coarse PCG, whose inner solve reads back
+   //     and verifies its own scalars) is different.  Before applying it the host synchronises and looks at the
+   //     loop's state itself: after any stop, the tail's included, it is not applied again, so an inner solve can
+   //     neither run on a stopped loop's vectors nor raise over the outer loop's own stop, which finish() reports
+   //     below.  While the outer loop runs, the inner solve works one nesting level down (its own SolverWork and
+   //     LoopDriver) and ends with the stream synchronised.
+   for (int i = 1;; i++)
    {
-      // the device-driven loop's state, reset before the read-back below idles the stream
-      w.loop.reset(s);
-      if (nen > 0) { cmult_den(d, z, nullptr, nullptr); }
-      else
+      if (i > 1 && w.loop.stopped_by(i - 1, s, "PCG")) { break; }
+      if (i > 1 && B.syncs && w.loop.stopped_after_sync(s)) { break; }
+      const kern::PcgStop stop{r0, i, max_iter, p.ctl, w.loop.mirror()};
+      B.step_r(p, stop);
+      if (i >= max_iter) { break; }
+      B.update_xd(p);
+      // ap = A d, den = (A d, d) and its test (after ++i: final_iter = i + 1 on a den == 0 stop)
+      const kern::PcgStop dstop{r0, i + 1, max_iter, p.ctl, w.loop.mirror(), p.betanom, 1};
+      cmult_den(p.ctl, &dstop);
+      std::swap(p.nom, p.betanom);  // nom <- betanom
+   }
+   // the stopping iteration's x += alpha d (a betanom stop)
+   kern::pcg_finish_x(n, p.alpha, p.d, x, s, p.ctl);
+   const kern::LoopCtl end = w.loop.finish(s);
+   ECM2_VERIFY(end.done != kern::PCG_RUNNING, ERR_INTERNAL, "device PCG loop ended without a stop");
+   const double bn = end.final;
+   ECM2_VERIFY(end.done != kern::PCG_NONFINITE, ERR_NUMERIC,
+               "PCG: non-finite (B r, r) or (A d, d) at iteration " << end.iters << " (" << bn << ")");
+   res.final_norm = bn >= 0 ? std::sqrt(bn) : bn;
+   res.iterations = end.iters;
+   res.converged = end.done == kern::PCG_CONVERGED;
+   return res;
+}
+
+// OperatorJacobiSmoother, or none (dinv null): z is never stored, dinv is applied inside the two fused passes
+struct JacobiPrec final : PcgPrec
+{
+   double *dinv = nullptr;
+   explicit JacobiPrec(bool on) { jacobi = on; }
+   void setup(PcgState &p) override
+   {
+      if (!jacobi) { return; }
+      dinv = p.w.dinv.data();
+      jacobi_dinv(p.A, p.ess, p.n_ess, p.ap, dinv, p.s);
+   }
+   void first(PcgState &p) override
+   {
+      if (dinv) { kern::pcg_precond(p.n, dinv, p.r, p.ap, p.s); }
+      p.copy(p.d, dinv ? p.ap : p.r);
+   }
+   void step_r(PcgState &p, const kern::PcgStop &stop) override
+   {
+      // r -= alpha A d, betanom = r.(M^{-1} r) in one pass, its test
+      kern::pcg_step_r(p.n, p.nom, p.den, p.ap, p.r, dinv, p.partials, p.betanom, p.alpha, p.s, p.ctl,
+                       p.direct ? &stop : nullptr);
+      if (!p.direct)
       {
-         cmult(d, z);
-         dot(z, d, den);
-      }
-      const double den0 = readback(den);
-      ECM2_VERIFY(std::isfinite(den0), ERR_NUMERIC, "PCG: den = " << den0);
-      if (den0 != 0.0)
-      {
-         // CGSolver's loop (solvers.cpp:930-1000) driven by the device: the stopping tests run on
-         // the device after each r.z and each (A d, d) (in the dot's final pass, or in a one-thread
-         // kernel after the all-reduce), and once one stops every later vector kernel returns at once.
-         // The host enqueues iteration i as soon as the betanom test of i - 1 has run (it polls the
-         // mirror's progress mark; no host synchronisation of the stream), so the queue holds the
-         // rest of iteration i - 1 while it does, and it ends at the iteration the device stopped at:
-         // the same iteration on every rank, so the ranks issue the same collectives.  The iterates
-         // are CGSolver's (the same operations per entry, in its order; x += alpha d deferred into
-         // the next pass that reads d); at most the stopping iteration's Mult runs after the stop.
-         kern::LoopCtl *ctl = w.loop.ctl();
-         for (int i = 1;; i++)
-         {
-            if (i > 1 && w.loop.stopped_by(i - 1, s, "PCG")) { break; }
-            // r -= alpha A d, betanom = r.(M^{-1} r) in one pass, its test
-            const kern::PcgStop stop{r0, i, max_iter, ctl, w.loop.mirror()};
-            kern::pcg_step_r(n, nom, den, z, r, dinv, partials, betanom, alpha, s, ctl, direct ? &stop : nullptr);
-            if (!direct)
-            {
-               A.sum_scalars(betanom, 1, s);
-               kern::pcg_check(betanom, stop, s);
-            }
-            if (i >= max_iter) { break; }
-            // x += alpha d, d = M^{-1} r + beta d
-            kern::pcg_update_xd(n, nom, den, betanom, x, d, r, dinv, s, ctl);
-            // z = A d, den = (A d, d) and its test (after ++i: final_iter = i + 1 on a den == 0 stop)
-            const kern::PcgStop dstop{r0, i + 1, max_iter, ctl, w.loop.mirror(), betanom, 1};
-            if (nen > 0) { cmult_den(d, z, ctl, &dstop); }
-            else if (direct)
-            {
-               cmult(d, z);
-               kern::dot(n, d, z, partials, den, s, nullptr, ctl, &dstop);
-            }
-            else
-            {
-               cmult(d, z);
-               dot(d, z, den, ctl);
-               kern::pcg_check(den, dstop, s);
-            }
-            std::swap(nom, betanom);  // nom <- betanom
-         }
-         // the stopping iteration's x += alpha d (a betanom stop)
-         kern::pcg_finish_x(n, alpha, d, x, s, ctl);
-         const kern::LoopCtl end = w.loop.finish(s);
-         ECM2_VERIFY(end.done != kern::PCG_RUNNING, ERR_INTERNAL, "device PCG loop ended without a stop");
-         const double bn = end.final;
-         ECM2_VERIFY(end.done != kern::PCG_NONFINITE, ERR_NUMERIC,
-                     "PCG: non-finite (B r, r) or (A d, d) at iteration " << end.iters << " (" << bn << ")");
-         res.final_norm = bn >= 0 ? std::sqrt(bn) : bn;
-         res.iterations = end.iters;
-         res.converged = end.done == kern::PCG_CONVERGED;
+         p.A.sum_scalars(p.betanom, 1, p.s);
+         kern::pcg_check(p.betanom, stop, p.s);
       }
    }
-   ECM2_HIP(hipStreamSynchronize(s));
-   return res;
+   // x += alpha d, d = M^{-1} r + beta d
+   void update_xd(PcgState &p) override { kern::pcg_update_xd(p.n, p.nom, p.den, p.betanom, p.x, p.d, p.r, dinv, p.s, p.ctl); }
+};
+
+// The smoother and the cycle: z = B r is a vector of its own (SolverWork's z), serial operators only
+template <class Prec>
+struct StoredPrec : PcgPrec
+{
+   Prec &B;
+   explicit StoredPrec(Prec &b) : B(b) { stored_z = true; }
+   void first(PcgState &p) override
+   {
+      B.mult(p.r, p.w.z.data(), p.s);
+      p.copy(p.d, p.w.z.data());
+   }
+   // x += alpha d, d = z + beta d
+   void update_xd(PcgState &p) override { kern::pcg_update_xd_z(p.n, p.nom, p.den, p.betanom, p.x, p.d, p.w.z.data(), p.s, p.ctl); }
+};
+
+// OperatorChebyshevSmoother: its first term in the pass that updates r, its last in the pass that sums (r, z)
+struct ChebPrec final : StoredPrec<ChebyshevSmoother>
+{
+   explicit ChebPrec(ChebyshevSmoother &b) : StoredPrec(b) { n_ess = b.n_ess(); }
+   void step_r(PcgState &p, const kern::PcgStop &stop) override
+   {
+      const int order = B.order();
+      const double *c = B.coeffs(), *dinv = B.dinv();
+      // ap holds A d until the entry pass has consumed it, then the smoother's A~ t
+      double *z = p.w.z.data(), *t = p.w.ct.data();
+      const ConstrainedMult bmult{B.op(), B.ess(), B.n_ess(), p.w.saved.data(), p.s};
+      // r -= alpha A d and the smoother's first term: t = dinv .* r, z = c_0 t
+      kern::pcg_step_r_prec(p.n, p.nom, p.den, p.ap, p.r, dinv, c[0], order > 1 ? t : nullptr, z, p.partials, p.alpha,
+                            order == 1, p.s, p.ctl);
+      // its further terms: t = dinv .* (A~ t), z += c_k t; the last one sums betanom = (r, z)
+      for (int k = 1; k < order; k++)
+      {
+         const bool last = k + 1 == order;
+         bmult(t, p.ap);
+         kern::cheb_accum(p.n, dinv, p.ap, c[k], last ? nullptr : t, z, p.s, last ? p.r : nullptr, p.partials, p.ctl);
+      }
+      kern::dot_final(kern::kDotPartials, p.partials, p.betanom, p.s, p.ctl, &stop);
+   }
+};
+
+// Multigrid: one cycle between the pass that updates r and the pass that sums (r, z)
+struct MgPrec final : StoredPrec<Multigrid>
+{
+   explicit MgPrec(Multigrid &b) : StoredPrec(b) { syncs = b.coarse_pcg(); }
+   void step_r(PcgState &p, const kern::PcgStop &stop) override
+   {
+      kern::mg_pcg_step_r(p.n, p.nom, p.den, p.ap, p.r, p.alpha, p.s, p.ctl);  // r -= alpha A d
+      B.mult(p.r, p.w.z.data(), p.s);
+      kern::dot(p.n, p.r, p.w.z.data(), p.partials, p.betanom, p.s, nullptr, p.ctl, &stop);  // betanom = (r, z), its test
+   }
+};
+} // namespace
+
+PCGResult pcg_solve(LinOp &A, const int *ess, int n_ess, const double *b, double *x, double rel_tol,
+                    double abs_tol, int max_iter, bool jacobi, hipStream_t s)
+{
+   JacobiPrec B(jacobi);
+   return pcg_loop(A, B, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, s);
 }
 
 PCGResult pcg_solve(PAForm &A, const int *ess, int n_ess, const double *b, double *x, double rel_tol,
@@ -405,6 +524,27 @@ PCGResult pcg_solve(PAForm &A, const int *ess, int n_ess, const double *b, doubl
 {
    FormOp op(A);
    return pcg_solve(op, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, jacobi, s);
+}
+
+PCGResult pcg_solve_prec(LinOp &A, ChebyshevSmoother &S, const int *ess, int n_ess, const double *b, double *x,
+                         double rel_tol, double abs_tol, int max_iter, hipStream_t s)
+{
+   ECM2_VERIFY(!A.distributed(), ERR_UNSUPPORTED, "PCG with a Chebyshev smoother: distributed operators are not supported");
+   ECM2_VERIFY(S.size() == A.size(), ERR_ARG, "PCG: the smoother has size " << S.size() << ", the operator " << A.size());
+   ChebPrec B(S);
+   return pcg_loop(A, B, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, s);
+}
+
+PCGResult pcg_solve_mg(LinOp &A, Multigrid &M, const int *ess, int n_ess, const double *b, double *x, double rel_tol,
+                       double abs_tol, int max_iter, hipStream_t s)
+{
+   ECM2_VERIFY(!A.distributed(), ERR_UNSUPPORTED, "PCG with a multigrid cycle: distributed operators are not supported");
+   ECM2_VERIFY(!A.concatenated(), ERR_UNSUPPORTED,
+               "PCG with a multigrid cycle: a loopback group's vectors are not in the cycle's numbering");
+   ECM2_VERIFY(M.size() == A.size(), ERR_ARG,
+               "PCG: the multigrid's finest level has size " << M.size() << ", the operator " << A.size());
+   MgPrec B(M);
+   return pcg_loop(A, B, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, s);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -626,109 +766,6 @@ void ChebyshevSmoother::mult(const double *x, double *y, hipStream_t s)
    }
 }
 
-PCGResult pcg_solve_prec(LinOp &A, ChebyshevSmoother &B, const int *ess, int n_ess, const double *b, double *x,
-                         double rel_tol, double abs_tol, int max_iter, hipStream_t s)
-{
-   // refused before anything is enqueued, as in pcg_solve
-   ECM2_VERIFY(((uintptr_t)x % 16) == 0, ERR_ARG, "PCG: x must be 16-byte aligned (got " << (const void *)x << ")");
-   ECM2_VERIFY(!A.distributed(), ERR_UNSUPPORTED, "PCG with a Chebyshev smoother: distributed operators are not supported");
-   const int n = A.size();
-   ECM2_VERIFY(B.size() == n, ERR_ARG, "PCG: the smoother has size " << B.size() << ", the operator " << n);
-   PCGResult res;
-   const int nen = A.energy_parts();  // (A d, d) folded into the Mult where the operator can, as in pcg_solve
-   const int order = B.order();
-   const double *c = B.coeffs(), *dinv = B.dinv();
-   SolverWork &w = solver_work();
-   w.ensure(n, std::max(n_ess, B.n_ess()), false, false,
-            std::max({kern::kDotPartials, kern::step_parts(n), nen + kern::ess_parts(n_ess)}), true);
-   // ap holds A d until the entry pass has consumed it, then the smoother's A~ t
-   double *r = w.r.data(), *d = w.p.data(), *ap = w.ap.data(), *z = w.z.data(), *t = w.ct.data();
-   double *partials = w.partials.data();
-   double *nom = w.scal.data(), *den = w.scal.data() + 1, *betanom = w.scal.data() + 2, *alpha = w.scal.data() + 3;
-   auto readback = [&]() {
-      ECM2_HIP(hipStreamSynchronize(s));
-      return *(volatile double *)w.hs;
-   };
-   const ConstrainedMult cmult{A, ess, n_ess, w.saved.data(), s};
-   const ConstrainedMult bmult{B.op(), B.ess(), B.n_ess(), w.saved.data(), s};
-   auto cmult_den = [&](double *in, double *out, const kern::LoopCtl *ctl, const kern::PcgStop *stop) {
-      if (nen > 0)
-      {
-         cmult(in, out, partials);
-         kern::dot_final(nen + kern::ess_parts(n_ess), partials, den, s, ctl, stop, ctl ? nullptr : w.hs_dev);
-      }
-      else
-      {
-         cmult(in, out);
-         kern::dot(n, in, out, partials, den, s, ctl ? nullptr : w.hs_dev, ctl, stop);
-      }
-   };
-   if (n) { ECM2_HIP(hipMemcpyAsync(r, b, sizeof(double) * n, hipMemcpyDeviceToDevice, s)); }
-   if (n) { ECM2_HIP(hipMemsetAsync(x, 0, sizeof(double) * n, s)); }
-   // z = B r, d = z, nom = (d, r) (solvers.cpp:893-903)
-   B.mult(r, z, s);
-   if (n) { ECM2_HIP(hipMemcpyAsync(d, z, sizeof(double) * n, hipMemcpyDeviceToDevice, s)); }
-   kern::dot(n, d, r, partials, nom, s, w.hs_dev);
-   const double nom0 = readback();
-   ECM2_VERIFY(std::isfinite(nom0), ERR_NUMERIC, "PCG: nom = " << nom0);
-   res.initial_norm = nom0 >= 0 ? std::sqrt(nom0) : nom0;
-   res.final_norm = res.initial_norm;
-   if (nom0 < 0.0)
-   {
-      // the smoother is not positive definite (an estimate far below the largest eigenvalue): not converged,
-      // final_norm = nom (:905-917)
-      res.initial_norm = res.final_norm = nom0;
-      return res;
-   }
-   const double r0 = std::max(nom0 * rel_tol * rel_tol, abs_tol * abs_tol);
-   if (nom0 <= r0)
-   {
-      res.converged = true;
-      return res;
-   }
-   w.loop.reset(s);
-   cmult_den(d, ap, nullptr, nullptr);
-   const double den0 = readback();
-   ECM2_VERIFY(std::isfinite(den0), ERR_NUMERIC, "PCG: den = " << den0);
-   if (den0 == 0.0) { return res; }
-   // CGSolver's loop driven by the device exactly as pcg_solve's (see there); the betanom test runs in the
-   // final pass of the smoother's last term
-   kern::LoopCtl *ctl = w.loop.ctl();
-   for (int i = 1;; i++)
-   {
-      if (i > 1 && w.loop.stopped_by(i - 1, s, "PCG")) { break; }
-      const kern::PcgStop stop{r0, i, max_iter, ctl, w.loop.mirror()};
-      // r -= alpha A d and the smoother's first term: t = dinv .* r, z = c_0 t
-      kern::pcg_step_r_prec(n, nom, den, ap, r, dinv, c[0], order > 1 ? t : nullptr, z, partials, alpha, order == 1, s, ctl);
-      // its further terms: t = dinv .* (A~ t), z += c_k t; the last one sums betanom = (r, z)
-      for (int k = 1; k < order; k++)
-      {
-         const bool last = k + 1 == order;
-         bmult(t, ap);
-         kern::cheb_accum(n, dinv, ap, c[k], last ? nullptr : t, z, s, last ? r : nullptr, partials, ctl);
-      }
-      kern::dot_final(kern::kDotPartials, partials, betanom, s, ctl, &stop);
-      if (i >= max_iter) { break; }
-      // x += alpha d, d = z + beta d
-      kern::pcg_update_xd_z(n, nom, den, betanom, x, d, z, s, ctl);
-      // ap = A d, den = (A d, d) and its test (after ++i: final_iter = i + 1 on a den == 0 stop)
-      const kern::PcgStop dstop{r0, i + 1, max_iter, ctl, w.loop.mirror(), betanom, 1};
-      cmult_den(d, ap, ctl, &dstop);
-      std::swap(nom, betanom);  // nom <- betanom
-   }
-   // the stopping iteration's x += alpha d (a betanom stop)
-   kern::pcg_finish_x(n, alpha, d, x, s, ctl);
-   const kern::LoopCtl end = w.loop.finish(s);
-   ECM2_VERIFY(end.done != kern::PCG_RUNNING, ERR_INTERNAL, "device PCG loop ended without a stop");
-   const double bn = end.final;
-   ECM2_VERIFY(end.done != kern::PCG_NONFINITE, ERR_NUMERIC,
-               "PCG: non-finite (B r, r) or (A d, d) at iteration " << end.iters << " (" << bn << ")");
-   res.final_norm = bn >= 0 ? std::sqrt(bn) : bn;
-   res.iterations = end.iters;
-   res.converged = end.done == kern::PCG_CONVERGED;
-   return res;
-}
-
 // ---------------------------------------------------------------------------------------
 // Multigrid (V-cycle over caller-supplied levels) + CGSolver(prec = the cycle)
 // ---------------------------------------------------------------------------------------
@@ -789,13 +826,19 @@ void Multigrid::set_coarse_pcg(double rel_tol, int max_iter)
    coarse_max_iter_ = max_iter;
 }
 
+// R = X - A~ Y, A~ the DIAG_ONE constrained Mult (Z is free here: it holds A~ Y until the residual has read it)
+void Multigrid::residual(Level &l, const double *X, double *Y, hipStream_t s)
+{
+   const ConstrainedMult cmult{*l.A, l.ess.data(), l.n_ess, l.saved.data(), s};
+   cmult(Y, l.Z.data());
+   kern::mg_residual(l.n, X, l.Z.data(), l.R.data(), s);
+}
+
 // MultigridBase::SmoothingStep (fem/multigrid.cpp:147-177): zero: Y = S X; else R = X - A~ Y, Z = S R, Y += Z
 void Multigrid::smooth(Level &l, const double *X, double *Y, bool zero, hipStream_t s)
 {
    if (zero) { return l.S->mult(X, Y, s); }
-   const ConstrainedMult cmult{*l.A, l.ess.data(), l.n_ess, l.saved.data(), s};
-   cmult(Y, l.Z.data());  // (Z is free here: it holds A~ Y until the residual has read it)
-   kern::mg_residual(l.n, X, l.Z.data(), l.R.data(), s);
+   residual(l, X, Y, s);
    l.S->mult(l.R.data(), l.Z.data(), s);
    kern::mg_add(l.n, l.Z.data(), Y, s);
 }
@@ -822,9 +865,7 @@ void Multigrid::cycle(int level, const double *X, double *Y, hipStream_t s)
    // the residual, restricted: X[k-1] = P~^T (X - A~ Y), P~ the prolongation without its essential rows and
    // columns (RectangularConstrainedOperator::MultTranspose: the fine essential entries of the input zeroed, the
    // coarse essential entries of the output zeroed); Y[k-1] = 0 is the coarse level's zero guess
-   const ConstrainedMult cmult{*l.A, l.ess.data(), l.n_ess, l.saved.data(), s};
-   cmult(Y, l.Z.data());
-   kern::mg_residual(l.n, X, l.Z.data(), l.R.data(), s);
+   residual(l, X, Y, s);
    if (l.n_ess) { kern::set_values(l.n_ess, l.ess.data(), 0.0, l.R.data(), s); }
    c.P->mult_transpose(l.R.data(), c.X.data(), s);
    if (c.n_ess) { kern::set_values(c.n_ess, c.ess.data(), 0.0, c.X.data(), s); }
@@ -846,115 +887,6 @@ void Multigrid::mult(const double *x, double *y, hipStream_t s)
                "multigrid: x and y must be 16-byte aligned (got " << (const void *)x << ", " << (const void *)y << ")");
    ECM2_VERIFY(x != y, ERR_ARG, "multigrid: x and y must be distinct");
    cycle(levels() - 1, x, y, s);
-}
-
-PCGResult pcg_solve_mg(LinOp &A, Multigrid &B, const int *ess, int n_ess, const double *b, double *x, double rel_tol,
-                       double abs_tol, int max_iter, hipStream_t s)
-{
-   // refused before anything is enqueued, as in pcg_solve
-   ECM2_VERIFY(((uintptr_t)x % 16) == 0, ERR_ARG, "PCG: x must be 16-byte aligned (got " << (const void *)x << ")");
-   ECM2_VERIFY(!A.distributed(), ERR_UNSUPPORTED, "PCG with a multigrid cycle: distributed operators are not supported");
-   ECM2_VERIFY(!A.concatenated(), ERR_UNSUPPORTED,
-               "PCG with a multigrid cycle: a loopback group's vectors are not in the cycle's numbering");
-   const int n = A.size();
-   ECM2_VERIFY(B.size() == n, ERR_ARG, "PCG: the multigrid's finest level has size " << B.size() << ", the operator " << n);
-   PCGResult res;
-   const int nen = A.energy_parts();  // (A d, d) folded into the Mult where the operator can, as in pcg_solve
-   SolverWork &w = solver_work();
-   w.ensure(n, n_ess, false, false, std::max({kern::kDotPartials, kern::step_parts(n), nen + kern::ess_parts(n_ess)}), true);
-   double *r = w.r.data(), *d = w.p.data(), *ap = w.ap.data(), *z = w.z.data();
-   double *partials = w.partials.data();
-   double *nom = w.scal.data(), *den = w.scal.data() + 1, *betanom = w.scal.data() + 2, *alpha = w.scal.data() + 3;
-   auto readback = [&]() {
-      ECM2_HIP(hipStreamSynchronize(s));
-      return *(volatile double *)w.hs;
-   };
-   const ConstrainedMult cmult{A, ess, n_ess, w.saved.data(), s};
-   auto cmult_den = [&](double *in, double *out, const kern::LoopCtl *ctl, const kern::PcgStop *stop) {
-      if (nen > 0)
-      {
-         cmult(in, out, partials);
-         kern::dot_final(nen + kern::ess_parts(n_ess), partials, den, s, ctl, stop, ctl ? nullptr : w.hs_dev);
-      }
-      else
-      {
-         cmult(in, out);
-         kern::dot(n, in, out, partials, den, s, ctl ? nullptr : w.hs_dev, ctl, stop);
-      }
-   };
-   if (n) { ECM2_HIP(hipMemcpyAsync(r, b, sizeof(double) * n, hipMemcpyDeviceToDevice, s)); }
-   if (n) { ECM2_HIP(hipMemsetAsync(x, 0, sizeof(double) * n, s)); }
-   // z = B r, d = z, nom = (d, r) (solvers.cpp:893-903)
-   B.mult(r, z, s);
-   if (n) { ECM2_HIP(hipMemcpyAsync(d, z, sizeof(double) * n, hipMemcpyDeviceToDevice, s)); }
-   kern::dot(n, d, r, partials, nom, s, w.hs_dev);
-   const double nom0 = readback();
-   ECM2_VERIFY(std::isfinite(nom0), ERR_NUMERIC, "PCG: nom = " << nom0);
-   res.initial_norm = nom0 >= 0 ? std::sqrt(nom0) : nom0;
-   res.final_norm = res.initial_norm;
-   if (nom0 < 0.0)
-   {
-      // the cycle is not positive definite: not converged, final_norm = nom (:905-917)
-      res.initial_norm = res.final_norm = nom0;
-      return res;
-   }
-   const double r0 = std::max(nom0 * rel_tol * rel_tol, abs_tol * abs_tol);
-   if (nom0 <= r0)
-   {
-      res.converged = true;
-      return res;
-   }
-   w.loop.reset(s);
-   cmult_den(d, ap, nullptr, nullptr);
-   const double den0 = readback();
-   ECM2_VERIFY(std::isfinite(den0), ERR_NUMERIC, "PCG: den = " << den0);
-   if (den0 == 0.0) { return res; }
-   // CGSolver's loop driven by the device exactly as pcg_solve's (see there).  The order of events around a stop:
-   //  1. stopped_by(i - 1) answers for the stops found up to the betanom test of i - 1.  A stop the device finds
-   //     after that, in the (A d, d) test of i - 1's tail, carries iters = i and may not be visible yet, so the
-   //     host may enqueue iteration i once more; its own kernels (mg_pcg_step_r, dot, pcg_update_xd_z, the Mult's
-   //     test) return at once.
-   //  2. The cycle's kernels are not keyed on the loop state.  With the smoother as the coarse solve (a) a cycle
-   //     enqueued in such an iteration runs on the unchanged r and writes z and its own vectors, which nothing
-   //     after the loop reads (pcg_finish_x reads alpha, d and x): the result cannot change, and the cycle has no
-   //     host-side check that could raise.
-   //  3. With a coarse PCG (b) the cycle synchronises the stream and its inner solve reads back and verifies its
-   //     own scalars.  Before such a cycle the host therefore synchronises and looks at the outer loop's state
-   //     itself: after any stop, the tail's included, no further cycle is enqueued, so an inner solve can neither
-   //     run on a stopped loop's vectors nor raise over the outer loop's own stop, which finish() reports below.
-   //     While the outer loop runs, the inner solve works one nesting level down (its own SolverWork and
-   //     LoopDriver) and ends with the stream synchronised.
-   kern::LoopCtl *ctl = w.loop.ctl();
-   for (int i = 1;; i++)
-   {
-      if (i > 1 && w.loop.stopped_by(i - 1, s, "PCG")) { break; }
-      if (i > 1 && B.coarse_pcg() && w.loop.stopped_after_sync(s)) { break; }
-      const kern::PcgStop stop{r0, i, max_iter, ctl, w.loop.mirror()};
-      // r -= alpha A d
-      kern::mg_pcg_step_r(n, nom, den, ap, r, alpha, s, ctl);
-      // z = B r: one cycle
-      B.mult(r, z, s);
-      // betanom = (r, z) and its test
-      kern::dot(n, r, z, partials, betanom, s, nullptr, ctl, &stop);
-      if (i >= max_iter) { break; }
-      // x += alpha d, d = z + beta d
-      kern::pcg_update_xd_z(n, nom, den, betanom, x, d, z, s, ctl);
-      // ap = A d, den = (A d, d) and its test (after ++i: final_iter = i + 1 on a den == 0 stop)
-      const kern::PcgStop dstop{r0, i + 1, max_iter, ctl, w.loop.mirror(), betanom, 1};
-      cmult_den(d, ap, ctl, &dstop);
-      std::swap(nom, betanom);  // nom <- betanom
-   }
-   // the stopping iteration's x += alpha d (a betanom stop)
-   kern::pcg_finish_x(n, alpha, d, x, s, ctl);
-   const kern::LoopCtl end = w.loop.finish(s);
-   ECM2_VERIFY(end.done != kern::PCG_RUNNING, ERR_INTERNAL, "device PCG loop ended without a stop");
-   const double bn = end.final;
-   ECM2_VERIFY(end.done != kern::PCG_NONFINITE, ERR_NUMERIC,
-               "PCG: non-finite (B r, r) or (A d, d) at iteration " << end.iters << " (" << bn << ")");
-   res.final_norm = bn >= 0 ? std::sqrt(bn) : bn;
-   res.iterations = end.iters;
-   res.converged = end.done == kern::PCG_CONVERGED;
-   return res;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -195,7 +195,7 @@ public:
    const double *coeffs() const { return coeffs_; }
    // y = S x (x, y device vectors of size(), 16-byte aligned and distinct: ERR_ARG otherwise)
    void mult(const double *x, double *y, hipStream_t s);
-   // what pcg_solve_prec's fused passes take
+   // what the PCG's fused passes take (solvers.cpp ChebPrec)
    LinOp &op() { return A_; }
    const double *dinv() const { return dinv_.data(); }
    const int *ess() const { return ess_.data(); }
@@ -211,11 +211,13 @@ private:
    DeviceArray<double> dinv_, t_, h_, saved_;  // 1 / diag; the term (D^-1 A~)^k D^-1 x, A~ of it, its ess entries
 };
 
-// CGSolver::Mult (linalg/solvers.cpp:869-1004) with prec = B on the constrained A, x overwritten: pcg_solve's
-// loop (the same device-driven stops: (B r, r) < 0 before or inside the loop, (A d, d) == 0, non-finite ->
-// ERR_NUMERIC, converged, max_iter; the same folded (A d, d) where A offers it; the same deferred x += alpha d)
-// with z = B r stored: the smoother's first term in the pass that updates r, its last in the pass that sums
-// (r, z).  B must be of A's size (ERR_ARG); x 16-byte aligned (ERR_ARG); distributed operators: ERR_UNSUPPORTED.
+// CGSolver::Mult (linalg/solvers.cpp:869-1004) with prec = B on the constrained A, x overwritten.  The loop is the
+// one of pcg_solve (solvers.cpp pcg_loop: the same device-driven stops -- (B r, r) < 0 before or inside the loop,
+// (A d, d) == 0, non-finite -> ERR_NUMERIC, converged, max_iter -- the same folded (A d, d) where A offers it, the
+// same deferred x += alpha d); this function supplies the preconditioner: z = B r stored, the smoother's first term
+// in the pass that updates r, its last in the pass that sums (r, z).  Refused, in this order and before anything is
+// allocated or enqueued: distributed operators (ERR_UNSUPPORTED), B not of A's size (ERR_ARG), x not 16-byte
+// aligned (ERR_ARG, the loop's own check).
 PCGResult pcg_solve_prec(LinOp &A, ChebyshevSmoother &B, const int *ess_dev, int n_ess, const double *b, double *x,
                          double rel_tol, double abs_tol, int max_iter, hipStream_t s);
 
@@ -248,7 +250,7 @@ public:
    int levels() const { return (int)lv_.size(); }
    int size() const { return lv_.back().n; }
    void set_coarse_pcg(double rel_tol, int max_iter);
-   // the coarse solve synchronises the stream and may throw ERR_NUMERIC (what pcg_solve_mg orders its events by)
+   // the coarse solve synchronises the stream and may throw ERR_NUMERIC (what the PCG's loop orders its events by)
    bool coarse_pcg() const { return coarse_max_iter_ > 0; }
    void mult(const double *x, double *y, hipStream_t s);
 
@@ -262,6 +264,7 @@ private:
       DeviceArray<int> ess;
       DeviceArray<double> X, Y, R, Z, saved;
    };
+   void residual(Level &l, const double *X, double *Y, hipStream_t s);  // l.R = X - A~ Y
    void smooth(Level &l, const double *X, double *Y, bool zero, hipStream_t s);
    void cycle(int level, const double *X, double *Y, hipStream_t s);
    std::vector<Level> lv_;
@@ -270,11 +273,12 @@ private:
    int coarse_max_iter_ = 0;
 };
 
-// CGSolver::Mult (linalg/solvers.cpp:869-1004) with prec = the cycle on the constrained A, x overwritten:
-// pcg_solve_prec's loop (the same device-driven stops, the same folded (A d, d), the same deferred x += alpha d,
-// the same results and read-backs) with z = B r computed by the cycle between the pass that updates r and the pass
-// that sums (r, z).  B must be of A's size (ERR_ARG); x 16-byte aligned (ERR_ARG); distributed operators and a
-// loopback group as A: ERR_UNSUPPORTED.
+// CGSolver::Mult (linalg/solvers.cpp:869-1004) with prec = the cycle on the constrained A, x overwritten: the same
+// loop again (pcg_loop: the same stops, folded (A d, d), deferred x += alpha d, results and read-backs); this function
+// supplies the preconditioner: z = B r computed by one cycle between the pass that updates r and the pass that sums
+// (r, z), and, with a coarse PCG, the loop's synchronise-and-look before each cycle.  Refused, in this order and
+// before anything is allocated or enqueued: distributed operators and a loopback group as A (ERR_UNSUPPORTED), B not
+// of A's size (ERR_ARG), x not 16-byte aligned (ERR_ARG, the loop's own check).
 PCGResult pcg_solve_mg(LinOp &A, Multigrid &B, const int *ess_dev, int n_ess, const double *b, double *x, double rel_tol,
                        double abs_tol, int max_iter, hipStream_t s);
 

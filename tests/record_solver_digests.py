@@ -1,6 +1,7 @@
 """The cases of tests/test_gpu_solver_bitwise.py and the recorder of their digests.
 
     python3 tests/record_solver_digests.py [out.json]
+    python3 tests/record_solver_digests.py --prec [out.json]
 
 runs every case on cuda:0 through the public Python API, twice, and writes the SHA-256 of the float64
 bytes of each result with the exact iteration count, final norm and converged flag (default:
@@ -31,7 +32,27 @@ shared piece can still go wrong:
            and BiCGSTAB stages on the convective ones; 23 / BiCGSTAB with a source
 Each solver setup runs fixed work (rel_tol = 0), max_iter = 1 (the loop ends before any wait) and a
 converging solve.  SEQUENCE: solves of different sizes and methods in one process, each equal to the
-digest of the same solve alone (the workspace they share grows, shrinks in use, and changes method)."""
+digest of the same solve alone (the workspace they share grows, shrinks in use, and changes method).
+
+--prec: the second group and the second file, tests/golden/solver_prec_digests.json -- the PCG with a Chebyshev
+smoother and the PCG with a multigrid cycle as its preconditioner, under the same rules.  The committed file
+was recorded from the build of commit 9b6518a, the last one in which these two and the Jacobi PCG were three
+copies of CGSolver::Mult's loop (csrc/solvers.cpp pcg_solve, pcg_solve_prec, pcg_solve_mg): that commit's
+solvers are the reference the one loop must reproduce bit for bit.  The recorder ran in two fresh processes
+there, and the two files were byte-identical; no case had to be dropped.  Every case stays at p <= 2, whose
+diagonal (the smoothers' and the coarse PCG's dinv) is summed without atomics.
+  cheb-o1, -o2, -o3   the serial p = 2 form above, ChebyshevSmoother of order 1 (the entry pass sums betanom
+           itself, no term loop), 2 (one term, the last) and 3 (a middle term that stores t), the largest
+           eigenvalue by the power method from the library's own start vector: max_eig and the steps are
+           part of the digest, which pins power_method on the shared workspace
+  cheb-o2-noess       no essential dofs: the essential kernels are not launched
+  cheb-o2-energy      the snapshot form of record_ts_epilogue_digests.build_form on 4 x 4 x 4 (729 dofs),
+           EnergyParts() == 1: (A d, d) folded into the Mult inside the preconditioned loop; fixed and conv
+  mg-smoother, mg-coarse   levels p = 1 -> 2 on the serial mesh (120 -> 693 dofs), mass + diffusion on both,
+           order-2 smoothers, pre = post = 1; the coarsest level's smoother, or a coarse PCG (1e-2, 200): the
+           nested workspace and the synchronise-and-look before each cycle
+  ode-23-cheb         one SDIRK33 step, the stage solves preconditioned by an order-2 smoother
+PREC_SEQUENCE: a nested solve, a depth-0 Jacobi solve, a preconditioned one and a BiCGSTAB on one workspace."""
 import hashlib
 import json
 import os
@@ -40,10 +61,11 @@ import sys
 import numpy as np
 
 DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "solver_digests.json")
+DIGESTS_PREC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "solver_prec_digests.json")
 CDT = 0.4359 * 0.05
 CONV_SCALE = 20.0
 MARKER = [0, 1, 1]
-MESHES = {"p2": (5, 4, 3, 2), "p3": (4, 3, 3, 3)}
+MESHES = {"p1": (5, 4, 3, 1), "p2": (5, 4, 3, 2), "p3": (4, 3, 3, 3)}
 # solver runs per setup: name -> (rel_tol, max_iter) for PCG and for BiCGSTAB
 PCG_RUNS = {"fixed": (0.0, 6), "one": (0.0, 1), "conv": (1e-10, 1000)}
 BCG_RUNS = {"fixed": (0.0, 5), "one": (0.0, 1), "conv": (1e-12, 1000)}
@@ -52,6 +74,13 @@ PCG_PAR = ["group", "member"]
 BCG_SETUPS = ["p2-jacobi", "p2-plain", "p3-plain"]
 ODE_CASES = [(23, "pcg", False), (34, "pcg", False), (23, "bicgstab", True), (34, "bicgstab", False)]
 SEQUENCE = ["bcg-p3-plain-conv", "pcg-jacobi-conv", "pcg-group-conv", "bcg-p2-jacobi-conv", "bcg-p3-plain-conv"]
+# the second group: the PCG with a Chebyshev smoother or a multigrid cycle as its preconditioner
+MG_RUNS = {"fixed": (0.0, 4), "one": (0.0, 1), "conv": (1e-10, 1000)}
+CHEB_SETUPS = {"o1": PCG_RUNS, "o2": PCG_RUNS, "o3": PCG_RUNS, "o2-noess": PCG_RUNS,
+               "o2-energy": {r: PCG_RUNS[r] for r in ("fixed", "conv")}}
+MG_SETUPS = ["smoother", "coarse"]
+MG_COARSE_PCG = (1e-2, 200)
+PREC_SEQUENCE = ["mg-coarse-conv", "pcg-jacobi-conv", "cheb-o3-conv", "bcg-p2-jacobi-conv", "mg-coarse-conv"]
 _CACHE = {}
 
 
@@ -60,6 +89,12 @@ def all_cases():
     ids += ["bcg-%s-%s" % (s, r) for s in BCG_SETUPS for r in BCG_RUNS]
     ids += ["ode-%d-%s" % (t, s) for t, s, _ in ODE_CASES]
     return ids
+
+
+def prec_cases():
+    ids = ["cheb-%s-%s" % (s, r) for s, runs in CHEB_SETUPS.items() for r in runs]
+    ids += ["mg-%s-%s" % (s, r) for s in MG_SETUPS for r in MG_RUNS]
+    return ids + ["ode-23-cheb"]
 
 
 def sha(t):
@@ -129,7 +164,7 @@ def serial_form(E, torch, name, mass, diff_scale, conv_alpha, marked=False):
                 f.AddDomainIntegrator(ci)
         f.Assemble()
         info = f.info()
-        assert info["kernel"] == (E.KERNEL_TPE if MESHES[name][3] == 2 else E.KERNEL_LINE), info
+        assert info["kernel"] == (E.KERNEL_TPE if MESHES[name][3] <= 2 else E.KERNEL_LINE), info
         assert f.EnergyParts() == 0 and not f.CoefficientSnapshot()   # (A d, d) by the dot pass
         kept = int(np.count_nonzero(np.asarray(MARKER)[m.GetAttributes() - 1])) if marked else ne
         assert f.ConvectionInfo() == ((True, kept, True) if conv_alpha is not None else (False, 0, False)), f.ConvectionInfo()
@@ -249,18 +284,90 @@ def run_ode(E, torch, ode_type, solver, sourced):
     return {"u": sha(u), "solves": ns, "iterations": it, "converged": conv}
 
 
+def _solve_result(E, x, it, nrm, run, max_iter, **more):
+    conv = E.pcg_last_converged()
+    if run == "conv":
+        assert conv and 1 < it < max_iter, (it, conv)
+    else:
+        assert it == max_iter and not conv, (it, conv)
+    return dict({"x": sha(x), "iterations": it, "final_norm": float(nrm).hex(), "converged": conv}, **more)
+
+
+def _power_smoother(E, op, ess, order):
+    """An order-`order` smoother with the power method's estimate from the library's own start vector."""
+    sm = E.ChebyshevSmoother(op, ess=ess, order=order)
+    assert sm.order == order == len(sm.coeffs) and sm.power_steps > 0, (sm.order, sm.power_steps)
+    return sm
+
+
+def run_cheb(E, torch, setup, run):
+    rel_tol, max_iter = CHEB_SETUPS[setup][run]
+    order = int(setup[1])
+    if setup.endswith("energy"):
+        import record_ts_epilogue_digests as TS
+        fes, form, _keep = _cached(("energy",), lambda: TS.build_form(E, torch, (4, 4, 4), "structured", "bioheat"))
+        assert fes.ndofs == 729 and form.EnergyParts() == 1   # (A d, d) folded into the Mult
+        ess = _cached(("energy", "ess"), lambda: torch.as_tensor(np.asarray(fes.boundary_dofs(), dtype=np.int32)).cuda())
+        op = _cached(("op", "energy"), lambda: E.Operator(form))
+        b = _cached(("b", "energy"), lambda: _dev(torch, np.random.default_rng(13).uniform(0.0, 1.0, 729)))
+    else:
+        _, fes, _, ess = serial_setup(E, torch, "p2")
+        form = serial_form(E, torch, "p2", True, CDT, None)   # (asserts EnergyParts() == 0: the dot pass)
+        op = _cached(("op", "pcg"), lambda: E.Operator(form))
+        b = _cached(("b", "p2"), lambda: _dev(torch, np.random.default_rng(11).uniform(0.0, 1.0, 693)))
+        ess = None if setup.endswith("noess") else ess
+    assert op.size == fes.ndofs and op.size % 2 == 1
+    sm = _power_smoother(E, op, ess, order)
+    x = torch.full((op.size,), float("nan"), dtype=torch.float64, device="cuda")
+    it, nrm = op.PCG(b, x, ess=ess, rel_tol=rel_tol, max_iter=max_iter, prec=sm)
+    return _solve_result(E, x, it, nrm, run, max_iter, max_eig=float(sm.max_eig).hex(), power_steps=sm.power_steps)
+
+
+def run_mg(E, torch, setup, run):
+    rel_tol, max_iter = MG_RUNS[run]
+    names = ["p1", "p2"]
+    fess = [serial_setup(E, torch, nm)[1] for nm in names]
+    esss = [serial_setup(E, torch, nm)[3] for nm in names]
+    assert [f.ndofs for f in fess] == [120, 693]
+    ops = [_cached(("op", "mg", nm), lambda nm=nm: E.Operator(serial_form(E, torch, nm, True, CDT, None))) for nm in names]
+    tr = _cached(("mg", "transfer"), lambda: E.PRefinementTransfer(fess[0], fess[1]))
+    assert (tr.width, tr.height) == (120, 693)
+    sms = [_power_smoother(E, op, ess, 2) for op, ess in zip(ops, esss)]
+    B = E.Multigrid(ops, sms, [tr], esss, pre=1, post=1, coarse_pcg=MG_COARSE_PCG if setup == "coarse" else None)
+    b = _cached(("b", "p2"), lambda: _dev(torch, np.random.default_rng(11).uniform(0.0, 1.0, 693)))
+    x = torch.full((693,), float("nan"), dtype=torch.float64, device="cuda")
+    it, nrm = ops[1].PCG(b, x, ess=esss[1], rel_tol=rel_tol, max_iter=max_iter, prec=B)
+    return _solve_result(E, x, it, nrm, run, max_iter, max_eig=[float(s.max_eig).hex() for s in sms])
+
+
+def run_ode_cheb(E, torch, ode_type):
+    _, fes, _, ess = serial_setup(E, torch, "p2")
+    dt = 0.05
+    cdt = E.ode_implicit_coeff(ode_type) * dt
+    T = E.Operator(serial_form(E, torch, "p2", True, cdt, None))
+    K = E.Operator(serial_form(E, torch, "p2", False, 1.0, None))
+    X = fes.dof_coords()
+    u = _dev(torch, 37.0 + 20.0 * X[:, 0] * (1.0 - X[:, 1]) + 5.0 * X[:, 2] * X[:, 2])
+    sm = _power_smoother(E, T, ess, 2)
+    ns, it, conv = E.ode_step(ode_type, T, K, dt, u, ess=ess, rel_tol=1e-10, max_iter=500, prec=sm)
+    assert conv and ns == 3 and it > ns, (ns, it, conv)
+    return {"u": sha(u), "solves": ns, "iterations": it, "converged": conv, "max_eig": float(sm.max_eig).hex()}
+
+
 def run_case(E, torch, cid):
     kind, rest = cid.split("-", 1)
+    if cid == "ode-23-cheb":
+        return run_ode_cheb(E, torch, 23)
     if kind == "ode":
         t, solver = rest.split("-")
         return run_ode(E, torch, int(t), solver, dict(((a, b), c) for a, b, c in ODE_CASES)[(int(t), solver)])
     setup, run = rest.rsplit("-", 1)
-    return run_pcg(E, torch, setup, run) if kind == "pcg" else run_bcg(E, torch, setup, run)
+    return {"pcg": run_pcg, "bcg": run_bcg, "cheb": run_cheb, "mg": run_mg}[kind](E, torch, setup, run)
 
 
-def run_sequence(E, torch):
-    """The results of SEQUENCE's solves, run one after the other."""
-    return [run_case(E, torch, cid) for cid in SEQUENCE]
+def run_sequence(E, torch, sequence=SEQUENCE):
+    """The results of a sequence's solves, run one after the other."""
+    return [run_case(E, torch, cid) for cid in sequence]
 
 
 def main(argv):
@@ -270,9 +377,12 @@ def main(argv):
     import torch
     import ecm2_amd as E
     E.load_library()
-    out = argv[1] if len(argv) > 1 else DIGESTS
+    prec = "--prec" in argv[1:]
+    args = [a for a in argv[1:] if a != "--prec"]
+    out = args[0] if args else (DIGESTS_PREC if prec else DIGESTS)
+    cases, sequence = (prec_cases(), PREC_SEQUENCE) if prec else (all_cases(), SEQUENCE)
     digests, refused = {}, []
-    for cid in all_cases():
+    for cid in cases:
         first, second = run_case(E, torch, cid), run_case(E, torch, cid)
         print(cid, first, flush=True)
         if first != second:
@@ -280,9 +390,14 @@ def main(argv):
             print("  REFUSED: the second run gave", second, flush=True)
             continue
         digests[cid] = first
-    seq = run_sequence(E, torch)
-    for cid, got in zip(SEQUENCE, seq):
-        assert got == digests[cid], ("sequence", cid, got, digests[cid])
+    alone = dict(digests)
+    if prec:   # the sequence's solves of the first group: their digests in the first file
+        with open(DIGESTS) as fh:
+            alone.update(json.load(fh))
+    seq = run_sequence(E, torch, sequence)
+    for cid, got in zip(sequence, seq):
+        assert got == alone[cid], ("sequence", cid, got, alone[cid])
+    assert seq[0] == seq[-1]
     print("sequence equals the solves run alone")
     with open(out, "w") as fh:
         json.dump(digests, fh, indent=1, sort_keys=True)

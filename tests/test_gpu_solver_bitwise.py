@@ -55,3 +55,33 @@ def test_sequence_on_the_shared_workspace(digests):
         print(cid, g)
         assert g == digests[cid], cid + " in the sequence differs from the same solve alone"
     assert got[0] == got[-1]
+
+
+# The PCG with a Chebyshev smoother and with a multigrid cycle on the one CGSolver loop they share with the Jacobi
+# PCG (csrc/solvers.cpp pcg_loop): tests/golden/solver_prec_digests.json, recorded by the same recorder (--prec)
+# from the build of the last commit in which the three were separate copies of that loop.
+@pytest.fixture(scope="module")
+def prec_digests():
+    with open(R.DIGESTS_PREC) as fh:
+        return json.load(fh)
+
+
+def test_every_prec_case_has_a_digest(prec_digests):
+    assert sorted(prec_digests) == sorted(R.prec_cases())
+
+
+@pytest.mark.parametrize("cid", R.prec_cases())
+def test_prec_solver_bitwise(prec_digests, cid):
+    got = R.run_case(E, torch, cid)
+    print(cid, got)
+    assert got == prec_digests[cid], "differs from the recorded bytes"
+
+
+def test_prec_sequence_on_the_shared_workspace(digests, prec_digests):
+    """A nested solve (the cycle's coarse PCG), a depth-0 Jacobi solve, a preconditioned one and a BiCGSTAB."""
+    alone = dict(digests, **prec_digests)
+    got = R.run_sequence(E, torch, R.PREC_SEQUENCE)
+    for cid, g in zip(R.PREC_SEQUENCE, got):
+        print(cid, g)
+        assert g == alone[cid], cid + " in the sequence differs from the same solve alone"
+    assert got[0] == got[-1]
