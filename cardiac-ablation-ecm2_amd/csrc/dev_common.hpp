@@ -1,5 +1,6 @@
 // dev_common.hpp -- device-side helpers shared by the gfx950 kernel translation units
-// (k_setup.hip, k_tpe.hip, k_line.hip, k_misc.hip, k_lform.hip, k_bdr.hip, k_conv.hip, k_bicgstab.hip, k_cheb.hip, k_mg.hip, k_transfer.hip).  Included by .hip files only.
+// (k_setup.hip, k_tpe.hip, k_line.hip, k_misc.hip, k_lform.hip, k_bdr.hip, k_conv.hip, k_pcg.hip, k_bicgstab.hip, k_cheb.hip, k_mg.hip, k_transfer.hip).  Included by .hip files only.
+// (The solvers' 16-byte vector passes: vec_pass.hpp.)
 #pragma once
 
 #include "kernels.hpp"
@@ -157,24 +158,7 @@ __device__ __forceinline__ CBasis *stage_basis(const Basis1D *tab)
    return p;
 }
 
-// ---- the 16-byte vector passes (k_cheb.hip, k_mg.hip) ----
-// One thread's pairs i = t, t + stride, ... < n / 2 of a grid-stride sweep over an FP64 vector read two entries at a
-// time; the thread stride - 1 also takes entry n - 1 of an odd n.
-struct Sweep
-{
-   long n2, stride, t;
-   bool tail;
-   __device__ explicit Sweep(int n)
-      : n2(n / 2), stride((long)gridDim.x * blockDim.x), t((long)blockIdx.x * blockDim.x + threadIdx.x),
-        tail((n & 1) && t == stride - 1)
-   {
-   }
-};
-
-__device__ inline const v2d *as2(const double *p) { return reinterpret_cast<const v2d *>(p); }
-__device__ inline v2d *as2(double *p) { return reinterpret_cast<v2d *>(p); }
-
-// ---- deterministic sums and the device-driven solver loops (k_misc.hip: PCG, k_bicgstab.hip: BiCGSTAB) ----
+// ---- deterministic sums and the device-driven solver loops (k_pcg.hip: PCG, k_bicgstab.hip: BiCGSTAB) ----
 // Pass 1 of a deterministic sum: one partial per workgroup of 256, partials[blockIdx.x] (a fixed order within
 // the workgroup); `red`: 4 doubles of LDS.
 __device__ __forceinline__ void park_partial(double s, double *__restrict__ partials, double *red)

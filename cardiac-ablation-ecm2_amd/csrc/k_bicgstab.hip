@@ -1,15 +1,15 @@
 // k_bicgstab.hip -- the vector passes of the device BiCGSTAB (gfx950): BiCGSTABSolver::Mult's iteration
 // (linalg/solvers.cpp:1650-1784) around its two Mults, fused into five passes of 16-byte accesses
 //   bcg_update_p   6 streams   p = r + beta (p - omega v), phat = dinv .* p
-//   bcg_dot        2           (r~, v)
+//   dot_partials   2           (r~, v)                                             (k_pcg.hip)
 //   bcg_update_s   5           s = r - alpha v (into r), shat = dinv .* s, ||s||^2
-//   bcg_dot        2           (t, s) and (t, t) in one pass
+//   dot_partials   2           (t, s) and (t, t) in one pass
 //   bcg_update_xr  8           x = (x + alpha phat) + omega shat, r = s - omega t, ||r||^2, (r~, r)
 // -- 23 vector streams an iteration.  Each pass that reduces parks one partial per workgroup in a fixed
 // order (dev_common.hpp park_partial) and a one-workgroup final pass sums them in a fixed order (no atomics:
 // two solves are bitwise equal) and runs the reference's stopping decision (bicgstab_stop.hpp) on the device;
 // once one stops, every later kernel of the solve returns at once (kernels.hpp, LoopCtl).
-#include "dev_common.hpp"
+#include "vec_pass.hpp"
 #include "bicgstab_stop.hpp"
 
 #include <algorithm>
@@ -23,48 +23,10 @@ using kern::LoopCtl;
 using kern::BcgScal;
 using kern::BcgFinal;
 
-// The read-only reductions take k_dot_partial's flat grid of contiguous chunks (workgroup b sums pairs
-// [b kChunk, (b + 1) kChunk)); the passes that write vectors and park partials take k_pcg_step_r's
-// grid-stride form over kBlocks workgroups (see the comment there).
-constexpr int kK = 4, kChunk = 256 * kK, kBlocks = 1024;
-
-// lists 0 and 1 (stride np): the partials of (a, b) and, with c, of (a, c); c == a: a read once
-__global__ void __launch_bounds__(256)
-k_bcg_dot(int n, const double *__restrict__ a, const double *__restrict__ b, const double *c, int np,
-          double *__restrict__ partials, const LoopCtl *ctl)
-{
-   if (ctl->done) { return; }  // (wave-uniform)
-   __shared__ double red[8];
-   double s0 = 0.0, s1 = 0.0;
-   const long n2 = n / 2, base = (long)blockIdx.x * kChunk + threadIdx.x;
-   const v2d *a2 = reinterpret_cast<const v2d *>(a), *b2 = reinterpret_cast<const v2d *>(b);
-   const v2d *c2 = reinterpret_cast<const v2d *>(c);
-   const bool self = c == a;
-#pragma unroll
-   for (int k = 0; k < kK; k++)
-   {
-      const long i = base + 256 * k;
-      if (i < n2)
-      {
-         const v2d u = a2[i], v = b2[i];
-         s0 += u.x * v.x;
-         s0 += u.y * v.y;
-         if (c)
-         {
-            const v2d w = self ? u : c2[i];
-            s1 += u.x * w.x;
-            s1 += u.y * w.y;
-         }
-      }
-   }
-   if ((n & 1) && blockIdx.x == gridDim.x - 1 && threadIdx.x == 255)
-   {
-      s0 += a[n - 1] * b[n - 1];
-      if (c) { s1 += a[n - 1] * c[n - 1]; }
-   }
-   park_partial(s0, partials, red);
-   if (c) { park_partial(s1, partials + np, red + 4); }
-}
+// The read-only reductions are kern::dot_partials' flat grid of contiguous chunks (k_pcg.hip); the direction is a
+// flat grid with a pair per thread; the passes that write vectors and park partials take k_pcg_step_r's grid-stride
+// form over kBlocks workgroups (see the comment there).  Each states its arithmetic once (vec_pass.hpp).
+constexpr int kBlocks = 1024;
 
 // The direction (solvers.cpp:1676-1693): it == 1 copies r; else beta = (rho_1 / rho_2) (alpha / omega),
 // p = p - omega v, p = r + beta p; then phat = M^{-1} p.  Reads p, v, r, dinv; writes p, phat.
@@ -73,38 +35,21 @@ k_bcg_update_p(int n, int it, const BcgScal *__restrict__ sc, double *__restrict
                const double *__restrict__ r, const double *__restrict__ dinv, double *__restrict__ phat,
                const LoopCtl *ctl)
 {
-   // entries 2i, 2i + 1 per lane (the last lane of an odd n takes the tail)
-   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x, n2 = n / 2;
-   if (i > n2 || ctl->done) { return; }
+   const Flat w(n);
+   if (w.t > w.n2 || ctl->done) { return; }
    const bool first = it == 1;
    const double omega = first ? 0.0 : sc->omega;
    const double beta = first ? 0.0 : (sc->rho1 / sc->rho2) * (sc->alpha / omega);
-   if (i < n2)
-   {
-      v2d *p2 = reinterpret_cast<v2d *>(p), *h2 = reinterpret_cast<v2d *>(phat);
-      const v2d *v2 = reinterpret_cast<const v2d *>(v), *r2 = reinterpret_cast<const v2d *>(r);
-      const v2d *q2 = reinterpret_cast<const v2d *>(dinv);
-      v2d pn = r2[i];
+   each_entry(w, n, [&](auto k) {
+      auto pn = ld(r, k);
       if (!first)
       {
-         const v2d t = p2[i] + (-omega) * v2[i];
+         const auto t = ld(p, k) + (-omega) * ld(v, k);
          pn = pn + beta * t;
       }
-      p2[i] = pn;
-      h2[i] = dinv ? q2[i] * pn : pn;
-   }
-   else if (n & 1)
-   {
-      const long j = n - 1;
-      double pn = r[j];
-      if (!first)
-      {
-         const double t = p[j] + (-omega) * v[j];
-         pn = pn + beta * t;
-      }
-      p[j] = pn;
-      phat[j] = dinv ? dinv[j] * pn : pn;
-   }
+      st(p, k, pn);
+      st(phat, k, dinv ? ld(dinv, k) * pn : pn);
+   });
 }
 
 // The first half step (solvers.cpp:1695-1730): alpha = rho_1 / (r~, v); s = r - alpha v, written into
@@ -119,25 +64,12 @@ k_bcg_update_s(int n, BcgScal *sc, double *__restrict__ r, const double *__restr
    __shared__ double red[4];
    const double alpha = sc->rho1 / sc->rtv;
    double s = 0.0;
-   const long n2 = n / 2, stride = (long)gridDim.x * blockDim.x, t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-   const v2d *v2 = reinterpret_cast<const v2d *>(v), *q2 = reinterpret_cast<const v2d *>(dinv);
-   v2d *r2 = reinterpret_cast<v2d *>(r), *h2 = reinterpret_cast<v2d *>(shat);
-   for (long i = t; i < n2; i += stride)
-   {
-      const v2d sn = r2[i] + (-alpha) * v2[i];
-      r2[i] = sn;
-      if (dinv) { h2[i] = q2[i] * sn; }
-      s += sn.x * sn.x;
-      s += sn.y * sn.y;
-   }
-   if ((n & 1) && t == stride - 1)  // the odd tail
-   {
-      const long i = n - 1;
-      const double sn = r[i] + (-alpha) * v[i];
-      r[i] = sn;
-      if (dinv) { shat[i] = dinv[i] * sn; }
-      s += sn * sn;
-   }
+   each_entry(Sweep(n), n, [&](auto k) {
+      const auto sn = ld(r, k) + (-alpha) * ld(v, k);
+      st(r, k, sn);
+      if (dinv) { st(shat, k, ld(dinv, k) * sn); }
+      dot_acc(s, sn, sn);
+   });
    park_partial(s, partials, red);
    // (every thread has read rho1 and rtv; nothing in this kernel reads alpha)
    if (blockIdx.x == 0 && threadIdx.x == 0) { sc->alpha = alpha; }
@@ -155,36 +87,16 @@ k_bcg_update_xr(int n, BcgScal *sc, double *__restrict__ x, const double *__rest
    __shared__ double red[8];
    const double alpha = sc->alpha, omega = sc->ts / sc->tt;
    double s0 = 0.0, s1 = 0.0;
-   const long n2 = n / 2, stride = (long)gridDim.x * blockDim.x, t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-   const v2d *ph2 = reinterpret_cast<const v2d *>(phat), *sh2 = reinterpret_cast<const v2d *>(shat);
-   const v2d *t2 = reinterpret_cast<const v2d *>(tv), *rt2 = reinterpret_cast<const v2d *>(rt);
-   v2d *x2 = reinterpret_cast<v2d *>(x), *r2 = reinterpret_cast<v2d *>(r);
-   for (long i = t; i < n2; i += stride)
-   {
-      const v2d sv = r2[i];
-      const v2d sh = shat ? sh2[i] : sv;
-      const v2d xa = x2[i] + alpha * ph2[i];
-      x2[i] = xa + omega * sh;
-      const v2d rn = sv + (-omega) * t2[i];
-      r2[i] = rn;
-      const v2d w = rt2[i];
-      s0 += rn.x * rn.x;
-      s0 += rn.y * rn.y;
-      s1 += w.x * rn.x;
-      s1 += w.y * rn.y;
-   }
-   if ((n & 1) && t == stride - 1)  // the odd tail
-   {
-      const long i = n - 1;
-      const double sv = r[i];
-      const double sh = shat ? shat[i] : sv;
-      const double xa = x[i] + alpha * phat[i];
-      x[i] = xa + omega * sh;
-      const double rn = sv + (-omega) * tv[i];
-      r[i] = rn;
-      s0 += rn * rn;
-      s1 += rt[i] * rn;
-   }
+   each_entry(Sweep(n), n, [&](auto k) {
+      const auto sv = ld(r, k);
+      const auto sh = shat ? ld(shat, k) : sv;
+      const auto xa = ld(x, k) + alpha * ld(phat, k);
+      st(x, k, xa + omega * sh);
+      const auto rn = sv + (-omega) * ld(tv, k);
+      st(r, k, rn);
+      dot_acc(s0, rn, rn);
+      dot_acc(s1, ld(rt, k), rn);
+   });
    park_partial(s0, partials, red);
    park_partial(s1, partials + np, red + 4);
    if (blockIdx.x == 0 && threadIdx.x == 0) { sc->omega = omega; }
@@ -254,7 +166,7 @@ k_bcg_final(int nparts, int np, const double *__restrict__ partials, BcgFinal f)
 namespace kern
 {
 
-int bcg_parts(int n) { return std::max(kBlocks, std::max(1, (int)((n / 2 + kChunk - 1) / kChunk))); }
+int bcg_parts(int n) { return std::max(kBlocks, step_parts(n)); }
 
 static void bcg_final(int nparts, int n, const double *partials, const BcgFinal &f, hipStream_t s)
 {
@@ -264,10 +176,7 @@ static void bcg_final(int nparts, int n, const double *partials, const BcgFinal 
 
 void bcg_dot(int n, const double *a, const double *b, const double *c, double *partials, const BcgFinal &f, hipStream_t s)
 {
-   const int nb = std::max(1, (int)((n / 2 + kChunk - 1) / kChunk));
-   hipLaunchKernelGGL(k_bcg_dot, dim3(nb), dim3(256), 0, s, n, a, b, c, bcg_parts(n), partials, f.ctl);
-   ECM2_HIP(hipGetLastError());
-   bcg_final(nb, n, partials, f, s);
+   bcg_final(dot_partials(n, a, b, c, bcg_parts(n), partials, s, f.ctl), n, partials, f, s);
 }
 
 void bcg_update_p(int n, int it, const BcgScal *sc, double *p, const double *v, const double *r, const double *dinv,

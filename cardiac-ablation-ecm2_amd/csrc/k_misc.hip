@@ -1,7 +1,7 @@
 // k_misc.hip -- reference-shaped pieces and vector kernels (gfx950): the workgroup-per-element
 // apply (E-vector AddMultPA, unfused Mult), ElementRestriction, the generic diagonal, the
-// deterministic summation pass of the fused kernels' scatter, halo pack/unpack, and the
-// device PCG / ODE vector kernels.
+// deterministic summation pass of the fused kernels' scatter, halo pack/unpack, the index kernels,
+// the one-thread-per-entry ODE vector kernels and the stream probes.  (The device PCG: k_pcg.hip.)
 #include "dev_common.hpp"
 
 #include <algorithm>
@@ -11,14 +11,6 @@ namespace ecm2
 namespace
 {
 using namespace dev;
-using kern::LoopCtl;
-using kern::PcgStop;
-using kern::PCG_RUNNING;
-using kern::PCG_CONVERGED;
-using kern::PCG_MAX_ITER;
-using kern::PCG_NEG_BR;
-using kern::PCG_DEN_ZERO;
-using kern::PCG_NONFINITE;
 
 // Workgroup per element (lane per quadrature point), any layout, L- or E-vectors in and
 // out (in_e / out_e): six 1D stages through LDS, the reference's smem kernels' structure
@@ -249,212 +241,6 @@ __global__ void k_copy_values(int n, const int *__restrict__ idx, const double *
    if (i < n) { y[idx[i]] = x[idx[i]]; }
 }
 
-
-// CGSolver's stopping tests (solvers.cpp:950-1000) as the device-driven loop runs them.
-// kind 0: the test of iteration `it` on betanom = (B r, r): not finite -> MFEM_VERIFY's abort
-// (PCG_NONFINITE, the host raises ECM2_ERR_NUMERIC); < 0 -> not converged (the preconditioner is not
-// positive definite, :955-964); <= r0 -> converged (:972-977); it + 1 > max_iter -> stopped (:979-982).
-// kind 1: the test of den = (A d, d) in iteration it's tail, after ++i (`it` is then the next
-// iteration's number, :993-1004): not finite -> abort; == 0 -> stopped, not converged, final_iter = it.
-__device__ void pcg_check_one(double v, const PcgStop &c)
-{
-   if (c.ctl->done) { return; }
-   int done;
-   double fin = v;
-   if (c.kind == 0)
-   {
-      done = !isfinite(v) ? PCG_NONFINITE
-             : v < 0.0    ? PCG_NEG_BR
-             : v <= c.r0  ? PCG_CONVERGED
-             : (c.it + 1 > c.max_iter ? PCG_MAX_ITER : PCG_RUNNING);
-   }
-   else
-   {
-      done = !isfinite(v) ? PCG_NONFINITE : (v == 0.0 ? PCG_DEN_ZERO : PCG_RUNNING);
-      fin = *c.betanom;  // (final_norm = sqrt(betanom) of the iteration, :1047)
-   }
-   if (done) { loop_set_done(c.ctl, c.host, done, c.it, fin); }
-   if (c.kind == 0) { loop_mark_checked(c.host, c.it); }
-}
-
-// Deterministic dot, pass 1: each workgroup writes its sum (park_partial: a fixed order per workgroup).  (A
-// one-pass form -- the last workgroup to arrive on a counter sums the parks -- was measured slower:
-// the 1,024 arrivals on one counter serialise, 16.6 vs 6.5 us per dot at a rank's 1.28M dofs,
-// profiles/r5/dot_probe.txt.)
-// (ctl: read only when no check writes it in the same kernel -- no __restrict__ on it)
-// A flat grid of contiguous chunks: workgroup b sums pairs [b kStepChunk, (b + 1) kStepChunk) -- grid-stride
-// loops stream 15-35% slower on this chip (profiles/r6/copy_probe.json: a 16-byte copy 6.67 TB/s flat against
-// 4.4-5.4 TB/s grid-stride).
-constexpr int kStepK = 4, kStepChunk = 256 * kStepK;
-__global__ void __launch_bounds__(256)
-k_dot_partial(int n, const double *__restrict__ a, const double *__restrict__ b, double *__restrict__ partials,
-              const LoopCtl *ctl)
-{
-   if (ctl && ctl->done) { return; }  // (wave-uniform)
-   __shared__ double red[4];
-   double s = 0.0;
-   const long n2 = n / 2, base = (long)blockIdx.x * kStepChunk + threadIdx.x;
-   const v2d *a2 = reinterpret_cast<const v2d *>(a), *b2 = reinterpret_cast<const v2d *>(b);
-#pragma unroll
-   for (int k = 0; k < kStepK; k++)
-   {
-      const long i = base + 256 * k;
-      if (i < n2)
-      {
-         const v2d u = a2[i], v = b2[i];
-         s += u.x * v.x;
-         s += u.y * v.y;
-      }
-   }
-   if ((n & 1) && blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) { s += a[n - 1] * b[n - 1]; }
-   park_partial(s, partials, red);
-}
-
-// pass 2 (one workgroup of kFinalThreads, sum_partials_fixed): the partials in a fixed order; with stop.ctl, a
-// stopping test on the result.
-__global__ void __launch_bounds__(kFinalThreads)
-k_dot_final(int nparts, const double *__restrict__ partials, double *__restrict__ out, double *__restrict__ hout,
-            const LoopCtl *ctl, PcgStop stop)
-{
-   if (ctl && ctl->done) { return; }
-   __shared__ double red[kFinalThreads / 64];
-   const double v = sum_partials_fixed(nparts, partials, red);
-   if (threadIdx.x != 0) { return; }
-   *out = v;
-   if (hout) { *hout = v; }  // mapped pinned host mirror (the solver's read-back)
-   if (stop.ctl) { pcg_check_one(v, stop); }
-}
-
-// The residual half of CGSolver's update (solvers.cpp:930-947): alpha = nom/den; r -= alpha A d;
-// z = dinv .* r (jacobi) and the partial sums of r.z (or r.r), one per workgroup in a fixed order,
-// finished by k_dot_final.  z holds A d on entry; z is not stored (k_pcg_update_xd forms it again from
-// r where it is consumed: 4 vector streams here instead of 8).  x += alpha d is deferred to
-// k_pcg_update_xd (or k_pcg_finish_x after the stop), which reads d anyway.  Same arithmetic per entry
-// as CGSolver's add / Mult(prec) / Dot.  alpha_out: alpha of the last step run.  16-byte accesses, a
-// grid-stride loop over kStepBlocks workgroups.  (The flat chunked grid of k_dot_partial was tried here
-// too: a GPU test later in the same process aborted in garbage collection with it, reproducibly, and
-// passed with this form -- profiles/r6/gpu5-gpu9; not diagnosed further, so this form stays.)
-constexpr int kStepBlocks = 1024;
-__global__ void __launch_bounds__(256)
-k_pcg_step_r(int n, const double *__restrict__ nom, const double *__restrict__ den, const double *__restrict__ z,
-             double *__restrict__ r, const double *__restrict__ dinv, double *__restrict__ partials,
-             double *__restrict__ alpha_out, const LoopCtl *ctl)
-{
-   if (ctl && ctl->done) { return; }
-   __shared__ double red[4];
-   const double alpha = *nom / *den;
-   if (blockIdx.x == 0 && threadIdx.x == 0) { *alpha_out = alpha; }
-   double s = 0.0;
-   const long n2 = n / 2, stride = (long)gridDim.x * blockDim.x, t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-   const v2d *z2 = reinterpret_cast<const v2d *>(z), *q2 = reinterpret_cast<const v2d *>(dinv);
-   v2d *r2 = reinterpret_cast<v2d *>(r);
-   for (long i = t; i < n2; i += stride)
-   {
-      const v2d rn = r2[i] + (-alpha) * z2[i];
-      r2[i] = rn;
-      if (dinv)
-      {
-         const v2d q = q2[i];
-         s += rn.x * (q.x * rn.x);
-         s += rn.y * (q.y * rn.y);
-      }
-      else
-      {
-         s += rn.x * rn.x;
-         s += rn.y * rn.y;
-      }
-   }
-   if ((n & 1) && t == stride - 1)  // the odd tail
-   {
-      const long i = n - 1;
-      const double rn = r[i] + (-alpha) * z[i];
-      r[i] = rn;
-      s += dinv ? rn * (dinv[i] * rn) : rn * rn;
-   }
-   park_partial(s, partials, red);
-}
-
-// The direction half (solvers.cpp:930, 985-990): x += alpha d (this iteration's alpha = nom/den,
-// deferred from k_pcg_step_r), then d = z + (betanom/nom) d with z = dinv .* r formed here.
-// 6 vector streams (x, d, r, dinv read; x, d written) instead of k_pcg_step's x part and
-// k_pcg_update_d's 3 + the stored z.
-__global__ void __launch_bounds__(256)
-k_pcg_update_xd(int n, const double *__restrict__ nom, const double *__restrict__ den,
-                const double *__restrict__ betanom, double *__restrict__ x, double *__restrict__ d,
-                const double *__restrict__ r, const double *__restrict__ dinv, const LoopCtl *ctl)
-{
-   // 16-byte accesses: entries 2i, 2i + 1 per lane (the last lane of an odd n takes the tail)
-   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x, n2 = n / 2;
-   if (i > n2 || (ctl && ctl->done)) { return; }
-   const double alpha = *nom / *den, beta = *betanom / *nom;
-   if (i < n2)
-   {
-      v2d *x2 = reinterpret_cast<v2d *>(x), *d2 = reinterpret_cast<v2d *>(d);
-      const v2d *r2 = reinterpret_cast<const v2d *>(r), *q2 = reinterpret_cast<const v2d *>(dinv);
-      const v2d dold = d2[i];
-      x2[i] = x2[i] + alpha * dold;
-      const v2d z = dinv ? q2[i] * r2[i] : r2[i];
-      d2[i] = z + beta * dold;
-   }
-   else if (n & 1)
-   {
-      const long j = n - 1;
-      const double dold = d[j];
-      x[j] = x[j] + alpha * dold;
-      const double z = dinv ? dinv[j] * r[j] : r[j];
-      d[j] = z + beta * dold;
-   }
-}
-
-// After the loop: the stopping iteration's x += alpha d, when the stop came from its betanom test
-// (converged, max_iter, (B r, r) < 0: CGSolver has already added alpha d then); a den == 0 stop
-// comes after k_pcg_update_xd has run (x complete).
-__global__ void k_pcg_finish_x(int n, const double *__restrict__ alpha, const double *__restrict__ d,
-                               double *__restrict__ x, const LoopCtl *ctl)
-{
-   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-   const int done = ctl->done;
-   if (i >= n || !(done == PCG_CONVERGED || done == PCG_MAX_ITER || done == PCG_NEG_BR)) { return; }
-   x[i] = x[i] + *alpha * d[i];
-}
-
-// ConstrainedOperator around a Mult without a vector copy: saved = v[ess], v[ess] = 0 ...
-__global__ void k_ess_save_zero(int n, const int *__restrict__ idx, double *__restrict__ v,
-                                double *__restrict__ saved)
-{
-   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-   if (i < n) { saved[i] = v[idx[i]]; v[idx[i]] = 0.0; }
-}
-
-// ... then v[ess] = y[ess] = saved (DIAG_ONE rows); sq_parts (optional): the block's sum of saved^2,
-// the ess rows' part of (A v, v) = (A v~, v~) + sum_ess v^2 with v~ = v, ess zeroed
-__global__ void __launch_bounds__(256)
-k_ess_restore(int n, const int *__restrict__ idx, const double *__restrict__ saved, double *__restrict__ v,
-              double *__restrict__ y, double *__restrict__ sq_parts)
-{
-   __shared__ double red[4];
-   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-   double sq = 0.0;
-   if (i < n)
-   {
-      const double sv = saved[i];
-      v[idx[i]] = sv;
-      y[idx[i]] = sv;
-      sq = sv * sv;
-   }
-   if (sq_parts) { park_partial(sq, sq_parts, red); }
-}
-
-__global__ void k_pcg_precond(int n, const double *__restrict__ dinv, const double *__restrict__ r,
-                              double *__restrict__ z)
-{
-   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-   if (i < n) { z[i] = dinv ? dinv[i] * r[i] : r[i]; }
-}
-
-// one thread: a stopping test after a distributed dot's all-reduce
-__global__ void k_pcg_check(const double *__restrict__ v, PcgStop stop) { pcg_check_one(*v, stop); }
-
 __global__ void k_scale(int n, double a, double *__restrict__ y)
 {
    const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -660,75 +446,6 @@ void copy_values(int n, const int *idx, const double *x, double *y, hipStream_t 
 {
    if (n == 0) { return; }
    hipLaunchKernelGGL(k_copy_values, dim3(grid_for(n, 256)), dim3(256), 0, s, n, idx, x, y);
-   ECM2_HIP(hipGetLastError());
-}
-
-int step_parts(int n) { return std::max(1, (int)((n / 2 + kStepChunk - 1) / kStepChunk)); }
-
-void dot(int n, const double *a, const double *b, double *partials, double *out, hipStream_t s, double *hout,
-         const LoopCtl *ctl, const PcgStop *stop)
-{
-   const int nb = step_parts(n);
-   hipLaunchKernelGGL(k_dot_partial, dim3(nb), dim3(256), 0, s, n, a, b, partials, ctl);
-   dot_final(nb, partials, out, s, ctl, stop, hout);
-}
-
-void pcg_step_r(int n, const double *nom, const double *den, const double *z, double *r, const double *dinv,
-                double *partials, double *out, double *alpha, hipStream_t s, const LoopCtl *ctl, const PcgStop *stop)
-{
-   hipLaunchKernelGGL(k_pcg_step_r, dim3(kStepBlocks), dim3(256), 0, s, n, nom, den, z, r, dinv, partials, alpha, ctl);
-   dot_final(kStepBlocks, partials, out, s, ctl, stop);
-}
-
-void pcg_update_xd(int n, const double *nom, const double *den, const double *betanom, double *x, double *d,
-                   const double *r, const double *dinv, hipStream_t s, const LoopCtl *ctl)
-{
-   if (n == 0) { return; }
-   hipLaunchKernelGGL(k_pcg_update_xd, dim3(grid_for(n / 2 + 1, 256)), dim3(256), 0, s, n, nom, den, betanom, x, d,
-                      r, dinv, ctl);
-   ECM2_HIP(hipGetLastError());
-}
-
-void pcg_finish_x(int n, const double *alpha, const double *d, double *x, hipStream_t s, const LoopCtl *ctl)
-{
-   if (n == 0) { return; }
-   hipLaunchKernelGGL(k_pcg_finish_x, dim3(grid_for(n, 256)), dim3(256), 0, s, n, alpha, d, x, ctl);
-   ECM2_HIP(hipGetLastError());
-}
-
-void pcg_check(const double *v, const PcgStop &stop, hipStream_t s)
-{
-   hipLaunchKernelGGL(k_pcg_check, dim3(1), dim3(1), 0, s, v, stop);
-   ECM2_HIP(hipGetLastError());
-}
-
-void ess_save_zero(int n, const int *idx, double *v, double *saved, hipStream_t s)
-{
-   if (n <= 0) { return; }
-   hipLaunchKernelGGL(k_ess_save_zero, dim3(grid_for(n, 256)), dim3(256), 0, s, n, idx, v, saved);
-   ECM2_HIP(hipGetLastError());
-}
-
-void ess_restore(int n, const int *idx, const double *saved, double *v, double *y, hipStream_t s, double *sq_parts)
-{
-   if (n <= 0) { return; }
-   hipLaunchKernelGGL(k_ess_restore, dim3(grid_for(n, 256)), dim3(256), 0, s, n, idx, saved, v, y, sq_parts);
-   ECM2_HIP(hipGetLastError());
-}
-
-int ess_parts(int n) { return n > 0 ? grid_for(n, 256) : 0; }
-
-void dot_final(int nparts, const double *partials, double *out, hipStream_t s, const LoopCtl *ctl,
-               const PcgStop *stop, double *hout)
-{
-   hipLaunchKernelGGL(k_dot_final, dim3(1), dim3(kFinalThreads), 0, s, nparts, partials, out, hout, ctl,
-                      stop ? *stop : PcgStop{});
-   ECM2_HIP(hipGetLastError());
-}
-
-void pcg_precond(int n, const double *dinv, const double *r, double *z, hipStream_t s)
-{
-   hipLaunchKernelGGL(k_pcg_precond, dim3(grid_for(n, 256)), dim3(256), 0, s, n, dinv, r, z);
    ECM2_HIP(hipGetLastError());
 }
 

@@ -1,9 +1,9 @@
 // kernels.hpp -- host launchers for the gfx950 HIP kernels (k_setup.hip: qdata and
 // coefficient setup; k_tpe.hip: thread-per-element p <= 2 apply and diagonal; k_line.hip:
 // line / brick p >= 3 apply and the sum-factorised diagonal; k_misc.hip: workgroup-per-element
-// apply, restriction, vector and solver kernels; k_lform.hip: the linear form's element vectors;
-// k_bdr.hip: the boundary-face terms; k_conv.hip: the convection term; k_bicgstab.hip: the BiCGSTAB loop's
-// vector passes; k_cheb.hip: the Chebyshev smoother's; k_mg.hip: the multigrid cycle's; k_transfer.hip: the
+// apply, restriction, index and one-thread-per-entry vector kernels; k_lform.hip: the linear form's element vectors;
+// k_bdr.hip: the boundary-face terms; k_conv.hip: the convection term; k_pcg.hip: the deterministic dot and the
+// device PCG's passes; k_bicgstab.hip: the BiCGSTAB loop's vector passes; k_cheb.hip: the Chebyshev smoother's; k_mg.hip: the multigrid cycle's; k_transfer.hip: the
 // p-refinement transfer operator, declared in transfer.hpp).
 //
 // Quadrature-data layouts (the qdata a PA form owns):
@@ -629,19 +629,45 @@ struct PcgStop
 constexpr int kDotPartials = 1024;
 void dot(int n, const double *a, const double *b, double *partials, double *out, hipStream_t s,
          double *hout = nullptr, const LoopCtl *ctl = nullptr, const PcgStop *stop = nullptr);
-// CGSolver's update in two passes (4 + 6 vector streams, z never stored):
-//   pcg_step_r: alpha = nom/den (-> *alpha); r -= alpha z (z holds A d); *out = r.(dinv .* r)
-//               (r.r without dinv), deterministic; stop (serial): betanom test in the same launch;
-//   pcg_update_xd: x += (nom/den) d; d = dinv .* r + (betanom/nom) d;
-//   pcg_finish_x (after the loop): x += *alpha d if the loop stopped at a betanom test.
-// the partial sums of dot's first pass (one per workgroup of its flat grid; pcg_step_r writes kDotPartials):
-// the partials buffer must hold them
+// the partial sums of dot's first pass (one per workgroup of its flat grid of contiguous chunks): the partials
+// buffer must hold them
 int step_parts(int n);
-void pcg_step_r(int n, const double *nom, const double *den, const double *z, double *r, const double *dinv,
-                double *partials, double *out, double *alpha, hipStream_t s, const LoopCtl *ctl = nullptr,
-                const PcgStop *stop = nullptr);
+// dot's first pass alone: list 0 = the partials of (a, b) and, with c, list 1 (at partials + np) = those of (a, c)
+// in one pass over a, b, c (c == a reads a once); returns the lists' length, step_parts(n)
+int dot_partials(int n, const double *a, const double *b, const double *c, int np, double *partials, hipStream_t s,
+                 const LoopCtl *ctl = nullptr);
+// CGSolver's update in two passes (k_pcg.hip).  The residual half, pcg_step_r: alpha = nom/den (-> *alpha);
+// r -= alpha ap (ap holds A d); then, in the same pass, the first piece of the preconditioner that follows:
+enum PcgStepAfter : int
+{
+   PCG_STEP_ONLY = 0,    // nothing (the multigrid cycle is applied to the stored r): 3 vector streams
+   PCG_STEP_JACOBI = 1,  // the partials of r.(dinv .* r) (dinv null: of r.r); z is not stored: 4 streams
+   PCG_STEP_CHEB = 2     // the smoother's first term, t = dinv .* r (t null, order 1: not stored), z = c0 t; sum
+                         // (order 1, z complete): the partials of r.z: 6 streams (5 at order 1)
+};
+// kDotPartials partials, for dot_final and its stopping test.  All vectors 16-byte aligned.
+struct PcgStepR
+{
+   int n = 0;
+   const double *nom = nullptr, *den = nullptr, *ap = nullptr;
+   double *r = nullptr, *alpha = nullptr;
+   const LoopCtl *ctl = nullptr;
+   PcgStepAfter after = PCG_STEP_ONLY;
+   const double *dinv = nullptr;  // JACOBI (optional), CHEB
+   double *partials = nullptr;    // JACOBI, CHEB with sum
+   double c0 = 0.0;               // CHEB
+   double *t = nullptr, *z = nullptr;
+   bool sum = false;
+};
+void pcg_step_r(const PcgStepR &a, hipStream_t s);
+// The direction half: x += (nom/den) d, then d = z + (betanom/nom) d with
+//   pcg_update_xd:   z = dinv .* r formed here (6 vector streams; dinv null: z = r), a flat grid;
+//   pcg_update_xd_z: the stored z = B r (5 streams), grid-stride.
+//   pcg_finish_x (after the loop): x += *alpha d if the loop stopped at a betanom test.
 void pcg_update_xd(int n, const double *nom, const double *den, const double *betanom, double *x, double *d,
                    const double *r, const double *dinv, hipStream_t s, const LoopCtl *ctl = nullptr);
+void pcg_update_xd_z(int n, const double *nom, const double *den, const double *betanom, double *x, double *d,
+                     const double *z, hipStream_t s, const LoopCtl *ctl);
 void pcg_finish_x(int n, const double *alpha, const double *d, double *x, hipStream_t s, const LoopCtl *ctl);
 // a stopping test alone (after a distributed dot's all-reduce)
 void pcg_check(const double *v, const PcgStop &stop, hipStream_t s);
@@ -706,8 +732,7 @@ struct BcgFinal
    BcgScal *sc = nullptr;
    double *out = nullptr, *hout = nullptr;
 };
-// lists 0, 1 = the partials of (a, b) and (a, c) in one pass over a, b, c (c null: list 0 alone; c == a reads
-// a once), a flat grid of contiguous chunks; then bcg_final(f)
+// dot_partials(a, b, c) on lists 0, 1 (c null: list 0 alone); then bcg_final(f)
 void bcg_dot(int n, const double *a, const double *b, const double *c, double *partials, const BcgFinal &f, hipStream_t s);
 // it == 1: p = r; else beta = (rho_1 / rho_2) (alpha / omega), p = r + beta (p - omega v); phat = dinv .* p
 // (dinv null: phat = p)
@@ -724,7 +749,7 @@ void bcg_update_xr(int n, BcgScal *sc, double *x, const double *phat, const doub
 // after the loop: x += alpha phat when it stopped at a ||s|| test
 void bcg_finish_x(int n, const BcgScal *sc, const double *phat, double *x, const LoopCtl *ctl, hipStream_t s);
 
-// ---- vector kernels of OperatorChebyshevSmoother, its power method and the PCG it preconditions (k_cheb.hip) ----
+// ---- vector kernels of OperatorChebyshevSmoother and its power method (k_cheb.hip) ----
 // The smoother y = sum_k c_k (D^-1 A~)^k D^-1 x term by term (linalg/solvers.cpp:619-658: t *= dinv, y += c_k t):
 //   cheb_first: t = dinv .* x, y = c0 t;
 //   cheb_accum: t = dinv .* h (h = A~ t_prev), y += ck t; with r: the partials of r.y (kDotPartials of them, for
@@ -733,15 +758,6 @@ void bcg_finish_x(int n, const BcgScal *sc, const double *phat, double *x, const
 void cheb_first(int n, const double *dinv, const double *x, double c0, double *t, double *y, hipStream_t s);
 void cheb_accum(int n, const double *dinv, const double *h, double ck, double *t, double *y, hipStream_t s,
                 const double *r = nullptr, double *partials = nullptr, const LoopCtl *ctl = nullptr);
-// CGSolver's update around a stored z = B r (linalg/solvers.cpp:930-990):
-//   pcg_step_r_prec: alpha = nom/den (-> *alpha); r -= alpha ap (ap holds A d); t = dinv .* r; z = c0 t; sum (order
-//                    1): the partials of r.z;
-//   pcg_update_xd_z: x += (nom/den) d; d = z + (betanom/nom) d.
-void pcg_step_r_prec(int n, const double *nom, const double *den, const double *ap, double *r, const double *dinv,
-                     double c0, double *t, double *z, double *partials, double *alpha, bool sum, hipStream_t s,
-                     const LoopCtl *ctl);
-void pcg_update_xd_z(int n, const double *nom, const double *den, const double *betanom, double *x, double *d,
-                     const double *z, hipStream_t s, const LoopCtl *ctl);
 // PowerMethod::EstimateLargestEigenvalue's step on D^-1 A~ (linalg/operator.cpp:871-928): v1 = dinv .* h with the
 // partials of (v0, v1) at partials[0, kDotPartials) and of (v1, v1) behind them; v *= 1 / sqrt(*norm); the
 // default start vector, an integer hash of the index in (0, 1) (k_cheb.hip, k_cheb_fill_hash).
@@ -750,14 +766,11 @@ void cheb_power_pass(int n, const double *dinv, const double *h, const double *v
 void cheb_scale(int n, const double *norm, double *v, hipStream_t s);
 void cheb_fill_hash(int n, double *v, hipStream_t s);
 
-// ---- vector kernels of the multigrid cycle and the PCG it preconditions (k_mg.hip) ----
+// ---- vector kernels of the multigrid cycle (k_mg.hip) ----
 // MultigridBase::SmoothingStep / Cycle (fem/multigrid.cpp:147-232): r = x - h (h = A~ y) in one pass; y += z.
-// CGSolver's residual update alone (linalg/solvers.cpp:930-947): alpha = nom/den (-> *alpha), r -= alpha ap.
 // All vectors 16-byte aligned.
 void mg_residual(int n, const double *x, const double *h, double *r, hipStream_t s);
 void mg_add(int n, const double *z, double *y, hipStream_t s);
-void mg_pcg_step_r(int n, const double *nom, const double *den, const double *ap, double *r, double *alpha, hipStream_t s,
-                   const LoopCtl *ctl);
 } // namespace kern
 
 } // namespace ecm2

@@ -285,6 +285,8 @@ struct PcgState
    {
       if (n) { ECM2_HIP(hipMemcpyAsync(dst, src, sizeof(double) * n, hipMemcpyDeviceToDevice, s)); }
    }
+   // the residual step's arguments up to what follows the update, which the preconditioner fills
+   kern::PcgStepR step_r() const { return kern::PcgStepR{n, nom, den, ap, r, alpha, ctl}; }
 };
 
 // What differs between CGSolver's preconditioners B: how z = B r enters an iteration, and which direction update
@@ -447,8 +449,12 @@ struct JacobiPrec final : PcgPrec
    void step_r(PcgState &p, const kern::PcgStop &stop) override
    {
       // r -= alpha A d, betanom = r.(M^{-1} r) in one pass, its test
-      kern::pcg_step_r(p.n, p.nom, p.den, p.ap, p.r, dinv, p.partials, p.betanom, p.alpha, p.s, p.ctl,
-                       p.direct ? &stop : nullptr);
+      kern::PcgStepR a = p.step_r();
+      a.after = kern::PCG_STEP_JACOBI;
+      a.dinv = dinv;
+      a.partials = p.partials;
+      kern::pcg_step_r(a, p.s);
+      kern::dot_final(kern::kDotPartials, p.partials, p.betanom, p.s, p.ctl, p.direct ? &stop : nullptr);
       if (!p.direct)
       {
          p.A.sum_scalars(p.betanom, 1, p.s);
@@ -486,8 +492,15 @@ struct ChebPrec final : StoredPrec<ChebyshevSmoother>
       double *z = p.w.z.data(), *t = p.w.ct.data();
       const ConstrainedMult bmult{B.op(), B.ess(), B.n_ess(), p.w.saved.data(), p.s};
       // r -= alpha A d and the smoother's first term: t = dinv .* r, z = c_0 t
-      kern::pcg_step_r_prec(p.n, p.nom, p.den, p.ap, p.r, dinv, c[0], order > 1 ? t : nullptr, z, p.partials, p.alpha,
-                            order == 1, p.s, p.ctl);
+      kern::PcgStepR a = p.step_r();
+      a.after = kern::PCG_STEP_CHEB;
+      a.dinv = dinv;
+      a.partials = p.partials;
+      a.c0 = c[0];
+      a.t = order > 1 ? t : nullptr;
+      a.z = z;
+      a.sum = order == 1;
+      kern::pcg_step_r(a, p.s);
       // its further terms: t = dinv .* (A~ t), z += c_k t; the last one sums betanom = (r, z)
       for (int k = 1; k < order; k++)
       {
@@ -505,7 +518,7 @@ struct MgPrec final : StoredPrec<Multigrid>
    explicit MgPrec(Multigrid &b) : StoredPrec(b) { syncs = b.coarse_pcg(); }
    void step_r(PcgState &p, const kern::PcgStop &stop) override
    {
-      kern::mg_pcg_step_r(p.n, p.nom, p.den, p.ap, p.r, p.alpha, p.s, p.ctl);  // r -= alpha A d
+      kern::pcg_step_r(p.step_r(), p.s);  // r -= alpha A d (PCG_STEP_ONLY)
       B.mult(p.r, p.w.z.data(), p.s);
       kern::dot(p.n, p.r, p.w.z.data(), p.partials, p.betanom, p.s, nullptr, p.ctl, &stop);  // betanom = (r, z), its test
    }

@@ -2,6 +2,7 @@
 
     python3 tests/record_solver_digests.py [out.json]
     python3 tests/record_solver_digests.py --prec [out.json]
+    python3 tests/record_solver_digests.py --sweep [out.json]
 
 runs every case on cuda:0 through the public Python API, twice, and writes the SHA-256 of the float64
 bytes of each result with the exact iteration count, final norm and converged flag (default:
@@ -52,7 +53,19 @@ diagonal (the smoothers' and the coarse PCG's dinv) is summed without atomics.
            order-2 smoothers, pre = post = 1; the coarsest level's smoother, or a coarse PCG (1e-2, 200): the
            nested workspace and the synchronise-and-look before each cycle
   ode-23-cheb         one SDIRK33 step, the stage solves preconditioned by an order-2 smoother
-PREC_SEQUENCE: a nested solve, a depth-0 Jacobi solve, a preconditioned one and a BiCGSTAB on one workspace."""
+PREC_SEQUENCE: a nested solve, a depth-0 Jacobi solve, a preconditioned one and a BiCGSTAB on one workspace.
+
+--sweep: the third group and the third file, tests/golden/solver_sweep_digests.json -- what the shapes above cannot
+reach in the solvers' 16-byte vector passes.  At 693 to 1,377 dofs no thread of a grid-stride pass (1,024 workgroups
+of 256, two entries per trip) makes a second trip round its loop, and all but one workgroup of a flat pass is partly
+empty; a second trip needs more than 2 x 256 x 1,024 = 524,288 entries.  One shape: 41 x 41 x 40 elements, p = 2,
+83 x 83 x 81 = 558,009 dofs (odd: the tail lane too), the moved vertices and polynomial coefficients of the serial
+form (per-point qdata, the thread-per-element kernel, the partial scatter: no atomics).  Fixed work only (rel_tol =
+0, three iterations): the Jacobi PCG; the PCG with an order-3 smoother (max_eig and the power steps in the digest);
+the PCG with the p = 1 -> 2 cycle whose coarsest level is its smoother; BiCGSTAB with Jacobi from the symmetric part
+on the form plus convection.  The committed file was recorded from the build of commit 18e996c, the last one in
+which every pass had a 16-byte body and a scalar copy of it for the tail entry: the recorder ran in two fresh
+processes there, and the two files were byte-identical; no case had to be dropped."""
 import hashlib
 import json
 import os
@@ -62,10 +75,11 @@ import numpy as np
 
 DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "solver_digests.json")
 DIGESTS_PREC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "solver_prec_digests.json")
+DIGESTS_SWEEP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "solver_sweep_digests.json")
 CDT = 0.4359 * 0.05
 CONV_SCALE = 20.0
 MARKER = [0, 1, 1]
-MESHES = {"p1": (5, 4, 3, 1), "p2": (5, 4, 3, 2), "p3": (4, 3, 3, 3)}
+MESHES = {"p1": (5, 4, 3, 1), "p2": (5, 4, 3, 2), "p3": (4, 3, 3, 3), "s1": (41, 41, 40, 1), "s2": (41, 41, 40, 2)}
 # solver runs per setup: name -> (rel_tol, max_iter) for PCG and for BiCGSTAB
 PCG_RUNS = {"fixed": (0.0, 6), "one": (0.0, 1), "conv": (1e-10, 1000)}
 BCG_RUNS = {"fixed": (0.0, 5), "one": (0.0, 1), "conv": (1e-12, 1000)}
@@ -81,6 +95,10 @@ CHEB_SETUPS = {"o1": PCG_RUNS, "o2": PCG_RUNS, "o3": PCG_RUNS, "o2-noess": PCG_R
 MG_SETUPS = ["smoother", "coarse"]
 MG_COARSE_PCG = (1e-2, 200)
 PREC_SEQUENCE = ["mg-coarse-conv", "pcg-jacobi-conv", "cheb-o3-conv", "bcg-p2-jacobi-conv", "mg-coarse-conv"]
+# the third group: one shape above the grid-stride passes' first trip, fixed work
+SWEEP_NDOFS = 83 * 83 * 81
+SWEEP_ITERS = 3
+SWEEP_SETUPS = ["pcg-jacobi", "cheb-o3", "mg-smoother", "bcg-jacobi"]
 _CACHE = {}
 
 
@@ -95,6 +113,10 @@ def prec_cases():
     ids = ["cheb-%s-%s" % (s, r) for s, runs in CHEB_SETUPS.items() for r in runs]
     ids += ["mg-%s-%s" % (s, r) for s in MG_SETUPS for r in MG_RUNS]
     return ids + ["ode-23-cheb"]
+
+
+def sweep_cases():
+    return ["sweep-" + s for s in SWEEP_SETUPS]
 
 
 def sha(t):
@@ -354,8 +376,43 @@ def run_ode_cheb(E, torch, ode_type):
     return {"u": sha(u), "solves": ns, "iterations": it, "converged": conv, "max_eig": float(sm.max_eig).hex()}
 
 
+def run_sweep(E, torch, setup):
+    """One fixed-work solve at SWEEP_NDOFS dofs."""
+    n = SWEEP_NDOFS
+    _, fes, _, ess = serial_setup(E, torch, "s2")
+    assert fes.ndofs == n and n % 2 == 1 and n > 2 * 256 * 1024
+    op = _cached(("op", "sweep"), lambda: E.Operator(serial_form(E, torch, "s2", True, CDT, None)))
+    b = _cached(("b", "s2"), lambda: _dev(torch, np.random.default_rng(11).uniform(0.0, 1.0, n)))
+    x = torch.full((n,), float("nan"), dtype=torch.float64, device="cuda")
+    if setup == "bcg-jacobi":
+        Top = _cached(("op", "sweepT"), lambda: E.Operator(serial_form(E, torch, "s2", True, CDT, CDT * CONV_SCALE)))
+        it, nrm = Top.BiCGSTAB(b, x, ess=ess, rel_tol=0.0, max_iter=SWEEP_ITERS, jacobi_of=op)
+        conv = E.bicgstab_last_converged()
+        assert it == SWEEP_ITERS and not conv, (it, conv)
+        return {"x": sha(x), "iterations": it, "final_norm": float(nrm).hex(), "converged": conv}
+    more = {}
+    if setup == "pcg-jacobi":
+        kw = {"jacobi": True}
+    elif setup == "cheb-o3":
+        sm = _power_smoother(E, op, ess, 3)
+        kw, more = {"prec": sm}, {"max_eig": float(sm.max_eig).hex(), "power_steps": sm.power_steps}
+    else:
+        assert setup == "mg-smoother", setup
+        fes1, ess1 = serial_setup(E, torch, "s1")[1], serial_setup(E, torch, "s1")[3]
+        op1 = _cached(("op", "sweep1"), lambda: E.Operator(serial_form(E, torch, "s1", True, CDT, None)))
+        tr = _cached(("sweep", "transfer"), lambda: E.PRefinementTransfer(fes1, fes))
+        assert (tr.width, tr.height) == (42 * 42 * 41, n)
+        sms = [_power_smoother(E, o, e, 2) for o, e in ((op1, ess1), (op, ess))]
+        kw = {"prec": E.Multigrid([op1, op], sms, [tr], [ess1, ess], pre=1, post=1)}
+        more = {"max_eig": [float(s.max_eig).hex() for s in sms]}
+    it, nrm = op.PCG(b, x, ess=ess, rel_tol=0.0, max_iter=SWEEP_ITERS, **kw)
+    return _solve_result(E, x, it, nrm, "fixed", SWEEP_ITERS, **more)
+
+
 def run_case(E, torch, cid):
     kind, rest = cid.split("-", 1)
+    if kind == "sweep":
+        return run_sweep(E, torch, rest)
     if cid == "ode-23-cheb":
         return run_ode_cheb(E, torch, 23)
     if kind == "ode":
@@ -377,10 +434,12 @@ def main(argv):
     import torch
     import ecm2_amd as E
     E.load_library()
-    prec = "--prec" in argv[1:]
-    args = [a for a in argv[1:] if a != "--prec"]
-    out = args[0] if args else (DIGESTS_PREC if prec else DIGESTS)
+    prec, sweep = "--prec" in argv[1:], "--sweep" in argv[1:]
+    args = [a for a in argv[1:] if a not in ("--prec", "--sweep")]
+    out = args[0] if args else (DIGESTS_SWEEP if sweep else DIGESTS_PREC if prec else DIGESTS)
     cases, sequence = (prec_cases(), PREC_SEQUENCE) if prec else (all_cases(), SEQUENCE)
+    if sweep:   # (one shape, fixed work: no sequence)
+        cases, sequence = sweep_cases(), []
     digests, refused = {}, []
     for cid in cases:
         first, second = run_case(E, torch, cid), run_case(E, torch, cid)
@@ -397,7 +456,7 @@ def main(argv):
     seq = run_sequence(E, torch, sequence)
     for cid, got in zip(sequence, seq):
         assert got == alone[cid], ("sequence", cid, got, alone[cid])
-    assert seq[0] == seq[-1]
+    assert not seq or seq[0] == seq[-1]
     print("sequence equals the solves run alone")
     with open(out, "w") as fh:
         json.dump(digests, fh, indent=1, sort_keys=True)

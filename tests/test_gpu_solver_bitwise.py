@@ -85,3 +85,23 @@ def test_prec_sequence_on_the_shared_workspace(digests, prec_digests):
         print(cid, g)
         assert g == alone[cid], cid + " in the sequence differs from the same solve alone"
     assert got[0] == got[-1]
+
+
+# What the shapes above cannot reach in the 16-byte vector passes (a second trip round a grid-stride loop, full flat
+# workgroups): tests/golden/solver_sweep_digests.json, one fixed-work solve per method at 558,009 dofs, recorded by the
+# same recorder (--sweep) from the build of the last commit in which every pass had a pair body and a scalar copy of it.
+@pytest.fixture(scope="module")
+def sweep_digests():
+    with open(R.DIGESTS_SWEEP) as fh:
+        return json.load(fh)
+
+
+def test_every_sweep_case_has_a_digest(sweep_digests):
+    assert sorted(sweep_digests) == sorted(R.sweep_cases())
+
+
+@pytest.mark.parametrize("cid", R.sweep_cases())
+def test_sweep_solver_bitwise(sweep_digests, cid):
+    got = R.run_case(E, torch, cid)
+    print(cid, got)
+    assert got == sweep_digests[cid], "differs from the recorded bytes"
