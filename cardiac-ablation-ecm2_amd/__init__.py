@@ -77,6 +77,8 @@ def load_library(path: str = LIB_PATH):
         "ecm2_mesh_cartesian_ex": (i32, [i32, i32, i32, f64, f64, f64, i32, pp]),
         "ecm2_mesh_read": (i32, [ctypes.c_char_p, pp]),
         "ecm2_mesh_refine_uniform": (i32, [vp]),
+        "ecm2_mesh_copy": (i32, [vp, pp]),
+        "ecm2_mesh_refinement_embedding": (i32, [vp, vp, vp]),
         "ecm2_mesh_info": (i32, [vp, ip, ip]),
         "ecm2_mesh_get_vertices": (i32, [vp, vp]),
         "ecm2_mesh_set_vertices": (i32, [vp, vp]),
@@ -247,6 +249,20 @@ class Mesh:
 
     def UniformRefinement(self):
         _check(_lib.ecm2_mesh_refine_uniform(self._h))
+
+    def Copy(self):
+        """Mesh(const Mesh &): an independent copy (a hierarchy keeps the mesh before and after UniformRefinement)."""
+        h = ctypes.c_void_p()
+        _check(_lib.ecm2_mesh_copy(self._h, ctypes.byref(h)))
+        return type(self)(_handle=h)
+
+    def refinement_embedding(self):
+        """(parent, octant), int32 [8 ne] each: the embedding of every element of the mesh that UniformRefinement of
+        this one produces (CoarseFineTransformations::embeddings; octant = ox + 2 oy + 4 oz in the parent's
+        lexicographic frame)."""
+        parent, octant = np.empty(8 * self.GetNE(), np.int32), np.empty(8 * self.GetNE(), np.int32)
+        _check(_lib.ecm2_mesh_refinement_embedding(self._h, _np_ptr(parent), _np_ptr(octant)))
+        return parent, octant
 
     def _info(self):
         nv, ne = ctypes.c_int(), ctypes.c_int()
@@ -975,6 +991,9 @@ _PAR_SIGS = {
                                           ctypes.c_void_p]),
     "ecm2_transfer_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "ecm2_transfer_create_h": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.POINTER(ctypes.c_void_p)]),
     "ecm2_transfer_mult": (ctypes.c_int, [ctypes.c_void_p] * 4),
     "ecm2_transfer_mult_transpose": (ctypes.c_int, [ctypes.c_void_p] * 4),
     "ecm2_transfer_info": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_int)] * 5
@@ -1417,22 +1436,11 @@ class ChebyshevSmoother:
         _check(_par_lib().ecm2_chebyshev_mult(self._h, _dev_ptr(x), _dev_ptr(y), _stream(stream)))
 
 
-class PRefinementTransfer:
-    """TensorProductPRefinementTransferOperator(lfes, hfes) (fem/transfer.cpp:2223-2592) between two H1Spaces of
-    orders lfes.order < hfes.order (1..4) on the same mesh, in either numbering: Mult prolongs a coarse L-vector,
-    MultTranspose restricts a fine one.  Only the spaces' gather maps are read."""
+class _Transfer:
+    """What the two transfer classes share: an ecm2_transfer handle between a coarse space of `width` dofs and a fine
+    one of `height`."""
 
-    def __init__(self, lfes, hfes):
-        if not isinstance(lfes, H1Space) or not isinstance(hfes, H1Space):
-            raise ECM2Error("lfes and hfes must be H1Spaces")
-        if lfes.ne != hfes.ne:
-            err = ECM2Error(f"ecm2 error 1: transfer: the spaces have {lfes.ne} and {hfes.ne} elements")
-            err.code = 1
-            raise err
-        gl, gh = lfes.gather_map(), hfes.gather_map()
-        h = ctypes.c_void_p()
-        _check(_par_lib().ecm2_transfer_create(lfes.ne, lfes.order, lfes.ndofs, _np_ptr(gl), hfes.order, hfes.ndofs,
-                                               _np_ptr(gh), ctypes.byref(h)))
+    def _adopt(self, h, lfes, hfes):
         self._h = h
         self.width, self.height = lfes.ndofs, hfes.ndofs
         pb = ctypes.c_long()
@@ -1457,11 +1465,53 @@ class PRefinementTransfer:
         _check(_par_lib().ecm2_transfer_mult_transpose(self._h, _dev_ptr(x), _dev_ptr(y), _stream(stream)))
 
 
+class PRefinementTransfer(_Transfer):
+    """TensorProductPRefinementTransferOperator(lfes, hfes) (fem/transfer.cpp:2223-2592) between two H1Spaces of
+    orders lfes.order < hfes.order (1..4) on the same mesh, in either numbering: Mult prolongs a coarse L-vector,
+    MultTranspose restricts a fine one.  Only the spaces' gather maps are read."""
+
+    def __init__(self, lfes, hfes):
+        if not isinstance(lfes, H1Space) or not isinstance(hfes, H1Space):
+            raise ECM2Error("lfes and hfes must be H1Spaces")
+        if lfes.ne != hfes.ne:
+            err = ECM2Error(f"ecm2 error 1: transfer: the spaces have {lfes.ne} and {hfes.ne} elements")
+            err.code = 1
+            raise err
+        gl, gh = lfes.gather_map(), hfes.gather_map()
+        h = ctypes.c_void_p()
+        _check(_par_lib().ecm2_transfer_create(lfes.ne, lfes.order, lfes.ndofs, _np_ptr(gl), hfes.order, hfes.ndofs,
+                                               _np_ptr(gh), ctypes.byref(h)))
+        self._adopt(h, lfes, hfes)
+
+
+class HRefinementTransfer(_Transfer):
+    """FiniteElementSpace::RefinementOperator (fem/fespace.cpp:1833-2120; what TransferOperator selects between two
+    meshes, fem/transfer.cpp:2055-) between an H1Space lfes on a mesh and the H1Space hfes of the same order (1..4)
+    on that mesh's UniformRefinement: Mult prolongs a coarse L-vector, MultTranspose restricts a fine one.  The
+    embedding is taken from the coarse mesh (Mesh.refinement_embedding); besides it only the spaces' gather maps
+    are read, so the coarse space may be in either numbering (a refined mesh has the entity numbering only)."""
+
+    def __init__(self, lfes, hfes):
+        if not isinstance(lfes, H1Space) or not isinstance(hfes, H1Space):
+            raise ECM2Error("lfes and hfes must be H1Spaces")
+        if lfes.order != hfes.order or hfes.ne != 8 * lfes.ne:
+            err = ECM2Error(f"ecm2 error 1: h-transfer: the spaces have orders {lfes.order} and {hfes.order} (equal "
+                            f"orders are needed) and {lfes.ne} and {hfes.ne} elements (8 children per parent)")
+            err.code = 1
+            raise err
+        gl, gh = lfes.gather_map(), hfes.gather_map()
+        parent, octant = lfes.mesh.refinement_embedding()
+        h = ctypes.c_void_p()
+        _check(_par_lib().ecm2_transfer_create_h(lfes.order, lfes.ne, lfes.ndofs, _np_ptr(gl), hfes.ne, hfes.ndofs,
+                                                 _np_ptr(gh), _np_ptr(parent), _np_ptr(octant), ctypes.byref(h)))
+        self._adopt(h, lfes, hfes)
+
+
 class Multigrid:
     """Multigrid's V-cycle (fem/multigrid.cpp:106-232) as GeometricMultigrid sets it up (:296-309: the
     prolongations' essential rows and columns removed) over levels 0 (coarsest) .. L - 1: ops, smoothers (a
     ChebyshevSmoother per level, built on that level's Operator and essential list), transfers (L - 1
-    PRefinementTransfers, level k -> k + 1), ess (a CUDA int32 tensor or None per level; copied).
+    PRefinementTransfers or HRefinementTransfers, level k -> k + 1), ess (a CUDA int32 tensor or None per level; copied).
     coarse_pcg: None -- the coarsest level's smoother applied once -- or (rel_tol, max_iter): a constrained
     Jacobi-PCG there (examples/ex26.cpp: (1e-2, 200)).  Mult: one cycle from a zero guess."""
 
@@ -1469,8 +1519,9 @@ class Multigrid:
         lib = _par_lib()
         L = len(ops)
         if any(not isinstance(o, Operator) for o in ops) or any(not isinstance(s, ChebyshevSmoother) for s in smoothers) \
-                or any(not isinstance(t, PRefinementTransfer) for t in transfers):
-            raise ECM2Error("ops, smoothers and transfers must be Operators, ChebyshevSmoothers and PRefinementTransfers")
+                or any(not isinstance(t, _Transfer) for t in transfers):
+            raise ECM2Error("ops, smoothers and transfers must be Operators, ChebyshevSmoothers and "
+                            "PRefinementTransfers or HRefinementTransfers")
         ess = [None] * L if ess is None else list(ess)
         # the C entry reads nlevels entries of every array (nlevels - 1 transfers): checked here, before the call
         if L < 1 or len(smoothers) != L or len(ess) != L or len(transfers) != L - 1:

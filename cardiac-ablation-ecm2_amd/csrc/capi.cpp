@@ -11,6 +11,7 @@
 #include "partition.hpp"
 #include "solvers.hpp"
 #include "transfer.hpp"
+#include "htransfer.hpp"
 
 #include <cstring>
 #include <memory>
@@ -46,7 +47,7 @@ struct ecm2_smoother
 };
 struct ecm2_transfer
 {
-   std::unique_ptr<ecm2::PTransfer> t;
+   std::unique_ptr<ecm2::Transfer> t;
 };
 struct ecm2_multigrid
 {
@@ -208,6 +209,32 @@ int ecm2_mesh_read(const char *path, ecm2_mesh **out)
 int ecm2_mesh_refine_uniform(ecm2_mesh *m)
 {
    return guard([&] { NEED(m); m->m.refine_uniform(); });
+}
+
+// Mesh(const Mesh &) (mesh/mesh.cpp: the copy constructor)
+int ecm2_mesh_copy(const ecm2_mesh *m, ecm2_mesh **out)
+{
+   return guard([&] {
+      NEED(m); NEED(out);
+      *out = nullptr;
+      *out = new ecm2_mesh{m->m};
+   });
+}
+
+// CoarseFineTransformations::embeddings of Mesh::UniformRefinement (mesh.cpp:10635-10705: child k of element i is
+// fine element 8 i + k and sits at the parent's native corner k)
+int ecm2_mesh_refinement_embedding(const ecm2_mesh *coarse, int *parent, int *octant)
+{
+   return guard([&] {
+      NEED(coarse); NEED(parent); NEED(octant);
+      int native_to_lex[8];
+      for (int a = 0; a < 8; a++) { native_to_lex[ecm2::kLexToNative[a]] = a; }
+      for (long e = 0; e < 8L * coarse->m.ne; e++)
+      {
+         parent[e] = (int)(e / 8);
+         octant[e] = native_to_lex[e % 8];
+      }
+   });
 }
 
 int ecm2_mesh_info(const ecm2_mesh *m, int *nv, int *ne)
@@ -1255,8 +1282,21 @@ int ecm2_transfer_create(int ne, int order_lo, int ndofs_lo, const int *gather_l
    return guard([&] {
       NEED(out);
       *out = nullptr;
-      *out = new ecm2_transfer{std::unique_ptr<ecm2::PTransfer>(
+      *out = new ecm2_transfer{std::unique_ptr<ecm2::Transfer>(
          new ecm2::PTransfer(ne, order_lo, ndofs_lo, gather_lo, order_hi, ndofs_hi, gather_hi))};
+   });
+}
+
+// ---- FiniteElementSpace::RefinementOperator (fem/fespace.cpp:1833-2120), TransferOperator's choice between two
+// meshes (fem/transfer.cpp:2055-) ----
+int ecm2_transfer_create_h(int order, int ne_lo, int ndofs_lo, const int *gather_lo, int ne_hi, int ndofs_hi,
+                           const int *gather_hi, const int *parent, const int *octant, ecm2_transfer **out)
+{
+   return guard([&] {
+      NEED(out);
+      *out = nullptr;
+      *out = new ecm2_transfer{std::unique_ptr<ecm2::Transfer>(
+         new ecm2::HTransfer(order, ne_lo, ndofs_lo, gather_lo, ne_hi, ndofs_hi, gather_hi, parent, octant))};
    });
 }
 
@@ -1299,7 +1339,7 @@ int ecm2_multigrid_create(int nlevels, ecm2_operator *const *ops, ecm2_smoother 
       ECM2_VERIFY(nlevels == 1 || transfers, ecm2::ERR_ARG, "null argument: transfers");
       std::vector<ecm2::LinOp *> o;
       std::vector<ecm2::ChebyshevSmoother *> sm;
-      std::vector<const ecm2::PTransfer *> tr;
+      std::vector<const ecm2::Transfer *> tr;
       std::vector<const int *> e;
       std::vector<int> ne;
       for (int k = 0; k < nlevels; k++)

@@ -783,7 +783,7 @@ void ChebyshevSmoother::mult(const double *x, double *y, hipStream_t s)
 // Multigrid (V-cycle over caller-supplied levels) + CGSolver(prec = the cycle)
 // ---------------------------------------------------------------------------------------
 Multigrid::Multigrid(const std::vector<LinOp *> &ops, const std::vector<ChebyshevSmoother *> &smoothers,
-                     const std::vector<const PTransfer *> &transfers, const std::vector<const int *> &ess_dev,
+                     const std::vector<const Transfer *> &transfers, const std::vector<const int *> &ess_dev,
                      const std::vector<int> &n_ess, int pre, int post, hipStream_t s)
    : pre_(pre), post_(post)
 {

@@ -224,7 +224,7 @@ PCGResult pcg_solve_prec(LinOp &A, ChebyshevSmoother &B, const int *ess_dev, int
 // Multigrid / MultigridBase (fem/multigrid.cpp:106-232: Mult, SmoothingStep, Cycle), V-cycle only, over levels 0
 // (coarsest) .. L - 1 that the caller supplies: each level's operator, its ChebyshevSmoother (built by the caller
 // on that level's operator and essential list), its essential list (device, copied) and the transfer k -> k + 1
-// (a PTransfer; Multigrid takes them as objects so that another kind of transfer can be added).  The essential
+// (a Transfer, transfer.hpp: a PTransfer between two orders, an HTransfer between a mesh and its refinement, mixed freely).  The essential
 // rows and columns of the prolongations are removed as GeometricMultigrid does (fem/multigrid.cpp:296-309,
 // RectangularConstrainedOperator): the coarse essential entries of the input and the fine essential entries of
 // the output are zero, and likewise for the transpose.
@@ -240,12 +240,12 @@ PCGResult pcg_solve_prec(LinOp &A, ChebyshevSmoother &B, const int *ess_dev, int
 // are not in the numbering of the transfers and essential lists): ERR_UNSUPPORTED.  x, y: device vectors of the finest
 // size, 16-byte aligned and distinct (ERR_ARG).  Operators, smoothers and transfers must outlive it.  Two cycles
 // are bitwise equal.
-class PTransfer;
+class Transfer;
 class Multigrid
 {
 public:
    Multigrid(const std::vector<LinOp *> &ops, const std::vector<ChebyshevSmoother *> &smoothers,
-             const std::vector<const PTransfer *> &transfers, const std::vector<const int *> &ess_dev,
+             const std::vector<const Transfer *> &transfers, const std::vector<const int *> &ess_dev,
              const std::vector<int> &n_ess, int pre, int post, hipStream_t s);
    int levels() const { return (int)lv_.size(); }
    int size() const { return lv_.back().n; }
@@ -259,7 +259,7 @@ private:
    {
       LinOp *A = nullptr;
       ChebyshevSmoother *S = nullptr;
-      const PTransfer *P = nullptr;  // this level -> the next finer one (null on the finest)
+      const Transfer *P = nullptr;   // this level -> the next finer one (null on the finest)
       int n = 0, n_ess = 0;
       DeviceArray<int> ess;
       DeviceArray<double> X, Y, R, Z, saved;

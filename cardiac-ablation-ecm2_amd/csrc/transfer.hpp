@@ -54,20 +54,36 @@ struct TransferPlan
 // dof that no element holds (it would never be written): ERR_ARG.
 TransferPlan build_transfer_plan(int ne, int pc, int nc, const int *gather_c, int pf, int nf, const int *gather_f);
 
+// What the multigrid cycle and the C handle hold: a transfer between a coarse and a fine space, whichever kind
+// (PTransfer below: two orders on one mesh; HTransfer, htransfer.hpp: one order on a mesh and its refinement).
+class Transfer
+{
+public:
+   virtual ~Transfer() = default;
+   virtual int ne() const = 0;        // elements of the fine space
+   virtual int order_lo() const = 0;
+   virtual int order_hi() const = 0;
+   virtual int width() const = 0;     // the coarse space's size (Operator::Width)
+   virtual int height() const = 0;    // the fine space's size (Operator::Height)
+   virtual size_t plan_bytes() const = 0;
+   virtual void mult(const double *x_c, double *y_f, hipStream_t s) const = 0;
+   virtual void mult_transpose(const double *x_f, double *y_c, hipStream_t s) const = 0;
+};
+
 // The device operator.  Vectors are device L-vectors of nc (coarse) and nf (fine) doubles; the kernels read and
 // write single entries through the maps, so no alignment beyond a double's is asked.  Two calls are bitwise equal.
-class PTransfer
+class PTransfer final : public Transfer
 {
 public:
    PTransfer(int ne, int pc, int nc, const int *gather_c, int pf, int nf, const int *gather_f);
-   int ne() const { return ne_; }
-   int order_lo() const { return pc_; }
-   int order_hi() const { return pf_; }
-   int width() const { return nc_; }   // the coarse space's size (Operator::Width)
-   int height() const { return nf_; }  // the fine space's size (Operator::Height)
-   size_t plan_bytes() const;          // both maps, the owner words and the transposed map on the device
-   void mult(const double *x_c, double *y_f, hipStream_t s) const;
-   void mult_transpose(const double *x_f, double *y_c, hipStream_t s) const;
+   int ne() const override { return ne_; }
+   int order_lo() const override { return pc_; }
+   int order_hi() const override { return pf_; }
+   int width() const override { return nc_; }
+   int height() const override { return nf_; }
+   size_t plan_bytes() const override;  // both maps, the owner words and the transposed map on the device
+   void mult(const double *x_c, double *y_f, hipStream_t s) const override;
+   void mult_transpose(const double *x_f, double *y_c, hipStream_t s) const override;
 
 private:
    int ne_, pc_, pf_, nc_, nf_;

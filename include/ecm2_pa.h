@@ -137,6 +137,13 @@ int ecm2_mesh_read(const char *path, ecm2_mesh **out);
 /* Mesh::UniformRefinement, mesh/mesh.cpp:11403 (hex: 1 -> 8; UniformRefinement3D_base's vertex
  * and child numbering, mesh.cpp:10155-10290, 10635-10705). */
 int ecm2_mesh_refine_uniform(ecm2_mesh *m);
+/* Mesh(const Mesh &), the copy constructor (mesh/mesh.hpp): an independent copy -- a hierarchy keeps the mesh
+ * before and after ecm2_mesh_refine_uniform. */
+int ecm2_mesh_copy(const ecm2_mesh *m, ecm2_mesh **out);
+/* CoarseFineTransformations::embeddings (Mesh::GetRefinementTransforms, mesh/mesh.hpp) of the mesh that
+ * ecm2_mesh_refine_uniform(coarse) produces: fine element e has parent e / 8 and sits at the parent's native corner
+ * e % 8 (mesh.cpp:10635-10705); octant = ox + 2 oy + 4 oz is that corner in the parent's lexicographic frame. */
+int ecm2_mesh_refinement_embedding(const ecm2_mesh *coarse, int *parent, int *octant /* host [8 ne_coarse] */);
 int ecm2_mesh_info(const ecm2_mesh *m, int *nv, int *ne);
 int ecm2_mesh_get_vertices(const ecm2_mesh *m, double *out /* host [nv][3] */);
 int ecm2_mesh_set_vertices(ecm2_mesh *m, const double *in /* host [nv][3] */);
@@ -557,6 +564,18 @@ int ecm2_ode_step_prec(int type, ecm2_operator *T, ecm2_operator *K, const doubl
 typedef struct ecm2_transfer ecm2_transfer;
 int ecm2_transfer_create(int ne, int order_lo, int ndofs_lo, const int *gather_lo, int order_hi, int ndofs_hi,
                          const int *gather_hi, ecm2_transfer **out);
+/* FiniteElementSpace::RefinementOperator (fem/fespace.cpp:1833-2120; local matrices GetLocalRefinementMatrices
+ * :1786-1807; what TransferOperator selects between two meshes, fem/transfer.cpp:2055-): the transfer between an H1
+ * space on a hex mesh (ne_lo elements) and the H1 space of the same order (1..4) on its uniform refinement (ne_hi = 8
+ * ne_lo), each given by its gather map, and the embedding of every fine element (host int [ne_hi]): its parent
+ * and its octant ox + 2 oy + 4 oz in the parent's lexicographic frame (ecm2_mesh_refinement_embedding).  Nothing
+ * else about the meshes is read.  The handle is ecm2_transfer_create's: ecm2_transfer_mult, _mult_transpose,
+ * _info, _destroy and ecm2_multigrid_create take it unchanged; _info reports order_lo = order_hi and ne = ne_hi.
+ * A null map or embedding, a map entry >= ndofs, a fine dof that no element holds, a parent or octant out of
+ * range: ECM2_ERR_ARG; an order outside 1..4, a negative (signed) entry, a parent without exactly one child per
+ * octant (non-conforming or partial refinement): ECM2_ERR_UNSUPPORTED. */
+int ecm2_transfer_create_h(int order, int ne_lo, int ndofs_lo, const int *gather_lo, int ne_hi, int ndofs_hi,
+                           const int *gather_hi, const int *parent, const int *octant, ecm2_transfer **out);
 /* Mult (fem/transfer.cpp:2542-2566, Prolongation3D :2338-2423): y_hi = P x_lo, device L-vectors of ndofs_lo and
  * ndofs_hi doubles; y_hi is overwritten, every entry once by its owner element (no zero fill, no atomics). */
 int ecm2_transfer_mult(ecm2_transfer *t, const double *x_lo, double *y_hi, void *stream);
