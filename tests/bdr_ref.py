@@ -19,6 +19,11 @@ map's rows (xi: v0 -> v1, eta: v0 -> v3).  dtype=np.longdouble restates the same
 precision: the float64 helper's own error, which keeps the GPU tolerance honest
 (tests/test_bdr_reference.py pins it).
 
+The componentwise criterion (tests/hp_ref.py's rule): pa_bound, mult_bound, diagonal_bound and
+assemble_bound are the same expressions over |B|, |x| and W |c| Dabs, Dabs = face_detj_bound (the
+corners) or |detJ| (a caller's array); hp_ref.C_BDR / C_BDR_DIAG / C_BDR_QD are derived in
+tests/test_bdr_reference.py.
+
 Integrators are (c, marker) pairs: c a scalar or per-point values [nbe][Q*Q]; marker None or 0 / 1
 per boundary attribute.
 """
@@ -46,6 +51,24 @@ def face_detj(bnodes, q1d, dtype=np.float64):
     return np.sqrt(np.sum(n * n, axis=1))
 
 
+def face_detj_bound(bnodes, q1d, dtype=np.float64):
+    """Dabs, the running magnitude of face_detj: the tangents over the |edge differences| (their convex
+    combinations), every cross-product component the SUM of the magnitudes of its two products, and the
+    norm of those three sums -- divided by nothing, so it is >= |x_xi x x_eta| with equality on a
+    planar axis-aligned face."""
+    t = O.gauss_legendre(q1d)[0].astype(dtype)
+    X = np.asarray(bnodes).astype(dtype)
+    one = dtype(1.0)
+    xi = np.tile(t, q1d)[None, None, :]
+    et = np.repeat(t, q1d)[None, None, :]
+    x0, x1, x2, x3 = (X[:, :, a, None] for a in range(4))
+    tx = (one - et) * np.abs(x1 - x0) + et * np.abs(x3 - x2)
+    ty = (one - xi) * np.abs(x2 - x0) + xi * np.abs(x3 - x1)
+    n = np.stack([tx[:, 1] * ty[:, 2] + tx[:, 2] * ty[:, 1], tx[:, 2] * ty[:, 0] + tx[:, 0] * ty[:, 2],
+                  tx[:, 0] * ty[:, 1] + tx[:, 1] * ty[:, 0]], 1)
+    return np.sqrt(np.sum(n * n, axis=1))
+
+
 def marker_keep(attr, marker):
     """markers[e] = attr[e] > 0 && marker[attr[e] - 1] (all faces without a marker)."""
     attr = np.asarray(attr)
@@ -65,6 +88,8 @@ class BdrRef:
         self.W = (w[None, :] * w[:, None]).reshape(-1)                # [q1 + Q q2]
         self.detJ = (np.asarray(detj).reshape(self.nbe, -1).astype(dtype) if detj is not None
                      else face_detj(bnodes, q1d, dtype))
+        # Dabs of the componentwise bounds: |detJ| of a caller's array (an exact input), else the corners'
+        self.Dabs = np.abs(self.detJ) if detj is not None else face_detj_bound(bnodes, q1d, dtype)
 
     # ---- AssemblePABoundary ----
     def pa_data(self, c, marker=None):
@@ -137,6 +162,47 @@ class BdrRef:
         for c, marker in integrators:
             self.add_transpose(self.face_lform(self.pa_data(c, marker)), b)
         return b
+
+    # ---- the running bounds S of the componentwise criterion (tests/hp_ref.py's rule): the same
+    # ---- expressions over |B|, |x| and W |c| Dabs
+    def pa_bound(self, c, marker=None):
+        """W |c| Dabs, [nbe][Q*Q]; zeros on the faces the marker excludes."""
+        if np.ndim(c) == 0:
+            cq = np.full(self.Dabs.shape, abs(c), self.dtype)
+        else:
+            cq = np.abs(np.asarray(c).reshape(self.nbe, -1).astype(self.dtype))
+        pa = self.W[None, :] * cq * self.Dabs
+        return np.where(marker_keep(self.attr, marker)[:, None], pa, self.dtype(0.0))
+
+    def _magnitudes(self):
+        """A copy of this reference over |B| (the face kernels then sum magnitudes only)."""
+        m = BdrRef.__new__(BdrRef)
+        m.__dict__.update(self.__dict__)
+        m.B = np.abs(self.B)
+        return m
+
+    def mult_bound(self, integrators, x):
+        m = self._magnitudes()
+        xf = m.gather(np.abs(np.asarray(x)))
+        yf = sum(m.face_apply(self.pa_bound(c, marker), xf) for c, marker in integrators)
+        return self.add_transpose(yf, np.zeros(self.ndofs, self.dtype))
+
+    def diagonal_bound(self, integrators):
+        """The diagonal's shared face vector over the magnitudes, with the same marker rule."""
+        D = self.p + 1
+        df = np.zeros((self.nbe, D, D), self.dtype)
+        for c, marker in integrators:
+            df += self.face_diag(self.pa_bound(c))
+            if marker is not None:
+                df[~marker_keep(self.attr, marker)] = 0
+        return self.add_transpose(df, np.zeros(self.ndofs, self.dtype))
+
+    def assemble_bound(self, integrators):
+        m = self._magnitudes()
+        S = np.zeros(self.ndofs, self.dtype)
+        for c, marker in integrators:
+            self.add_transpose(m.face_lform(self.pa_bound(c, marker)), S)
+        return S
 
 
 def lf_default_q1d(p):

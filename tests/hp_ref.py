@@ -23,7 +23,10 @@ is the worst constant of the CPU oracle over the case matrix -- of its two indep
 (PA and element-matrix) for C, of its diagonal for C_DIAG (tests/test_hp_reference.py measures both and
 checks the constants against them; DESIGN.md "Tolerance" has the tables and the reasoning).  C_CONV and
 C_CONV_QD are the same rule for the convection term's products and its qdata, whose reference and bound
-live in tests/conv_ref.py (measured by tests/test_conv_reference.py).
+live in tests/conv_ref.py (measured by tests/test_conv_reference.py).  C_LF / C_LF_JOULE
+(the device linear form: tests/lform_ref.py, tests/test_lform_reference.py) and C_BDR /
+C_BDR_DIAG / C_BDR_QD (the Robin face terms: tests/bdr_ref.py, tests/test_bdr_reference.py, section 4b) likewise,
+over the case matrix of tests/rhs_cases.py.
 """
 import numpy as np
 
@@ -51,6 +54,24 @@ C_CONV = 32.0
 # Its qdata alpha W adj(J) v against Pabs: c_ref = 7.14 (perturbed, p = 4, Q = 6), 4 * c_ref = 28.6 -> 32: two
 # roundings per Jacobian entry, a difference of two products per cofactor, three terms and two scalings.
 C_CONV_QD = 32.0
+# The device linear form (tests/lform_ref.py: LFRef.bound; tests/test_lform_reference.py measures it over
+# tests/rhs_cases.py).  Point, grid-function and affine sources: c_ref = 9.06 (the float64 checker, perturbed
+# 5 x 4 x 4, p = 4, Q = 5, the signed per-point source), 4 * c_ref = 36.2 -> 64.  The chains are the mass Mult's
+# second half -- three B^T stages and the dof's valence -- behind det J's 14 operations.
+C_LF = 64.0
+# The Joule source: c_ref = 3.19 (perturbed, p = 4, Q = 6, the electrode potential, constant sigma), 4 * c_ref =
+# 12.8 -> 16.  Smaller than C_LF because its F carries the gradient's own running bound: 2 |g| Sg is several
+# times |g|^2 even where nothing cancels.
+C_LF_JOULE = 16.0
+# The Robin face terms (tests/bdr_ref.py; tests/test_bdr_reference.py).  Mult (both of the checker's
+# evaluations) and the face linear form: c_ref = 7.75 (the face linear form, perturbed 5 x 4 x 3, p = 4, the
+# default 3-point rule, signed g), 4 * c_ref = 31.0 -> 32.
+C_BDR = 32.0
+# The face diagonal: c_ref = 8.39 (perturbed, p = 4, Q = 6), 4 * c_ref = 33.5 -> 64: Q^2 = 36 terms of one sign in
+# one running sum.
+C_BDR_DIAG = 64.0
+# The face qdata W c |x_xi x x_eta| against W |c| Dabs: c_ref = 4.87 (perturbed, p = 4, Q = 6), 4 * c_ref = 19.5 -> 32.
+C_BDR_QD = 32.0
 
 
 def _oracle():

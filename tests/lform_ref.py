@@ -11,6 +11,14 @@ restriction_mult_transpose).  dtype=np.longdouble restates the same formulas in 
 (its own trilinear geometry and reduction): the float64 helper's own error, which keeps the GPU
 tolerance honest.  tests/test_lform_reference.py pins it.
 
+The componentwise criterion (tests/hp_ref.py's rule; float64 tables and inputs are exact): LFRef.bound is
+S = R^T |B|^T |B|^T |B|^T (W F |det J|), the same expression with every factor replaced by its magnitude --
+point_bound is F, geometry_bound the running magnitudes of adj J and det J over conv_ref's edge-form |J|
+(|J| itself in Jacobian mode).  hp_ref.constant measures a float64 result against the np.longdouble
+instance's assemble and bound; hp_ref.C_LF / C_LF_JOULE are derived in tests/test_lform_reference.py.
+edge_form=True evaluates the trilinear map from its edge differences in any dtype (what the 80-bit
+reference uses, and the float64 checker where the coordinates are large against the edges).
+
 Sources are dicts: {"kind": "constant", "value"}, {"kind": "quad", "values" [ne][nq]},
 {"kind": "gridfunc", "field"}, {"kind": "affine", "field", "scale", "slope", "t_ref"},
 {"kind": "joule", "phi", "sigma", "slope", "t_ref", "T" (or None)}.
@@ -19,9 +27,11 @@ import os
 
 import numpy as np
 
+import conv_ref
 import helpers
 import oracle as O
 from helpers import GOLDEN
+from hp_ref import U
 
 
 def _adj(Jm):
@@ -66,8 +76,9 @@ class LFRef:
     """The linear form's reference on one space: p, q1d, gather map, and the geometry from the
     lexicographic corners (enodes [ne][3][8]) or from MFEM-layout Jacobians J [ne][3 (j)][3 (i)][nq]."""
 
-    def __init__(self, p, q1d, gm, ndofs, enodes=None, J=None, dtype=np.float64):
+    def __init__(self, p, q1d, gm, ndofs, enodes=None, J=None, dtype=np.float64, edge_form=False):
         self.p, self.q1d, self.ndofs, self.dtype = p, q1d, int(ndofs), dtype
+        self.enodes = None if J is not None else np.asarray(enodes)
         self.gm = np.asarray(gm)
         self.ne = self.gm.shape[0]
         B, G = O.dof_to_quad(p, q1d)                      # [Q][D]
@@ -75,6 +86,11 @@ class LFRef:
         self.W = O.cube_weights(q1d).astype(dtype)
         if J is not None:
             self.Jm = np.transpose(np.asarray(J), (0, 3, 2, 1)).astype(dtype)   # [e][q][i][j]
+            self.detJ = None
+        elif edge_form:
+            # the trilinear map from its edge differences (conv_ref._edge_jacobians), in `dtype`: a float64
+            # evaluation that stays accurate when the coordinates are large against the edges
+            self.Jm = conv_ref._edge_jacobians(self.enodes.astype(dtype), O.gauss_legendre(q1d)[0].astype(dtype))[0]
             self.detJ = None
         elif dtype == np.float64:
             _, Jo, detJ = O.geom(enodes, q1d)             # J [e][j][i][q]
@@ -103,13 +119,19 @@ class LFRef:
         B = self.B
         return np.einsum("xa,yb,zc,ecba->ezyx", B, B, B, self._evec(x)).reshape(self.ne, -1)
 
+    def ref_grad(self, x, magnitudes=False):
+        """The reference gradient at the points [ne][nq][3]; magnitudes: its running bound, the same sums
+        over |B|, |G| and |x|."""
+        xe, B, G = self._evec(x), self.B, self.G
+        if magnitudes:
+            xe, B, G = np.abs(xe), np.abs(B), np.abs(G)
+        return np.stack([np.einsum("xa,yb,zc,ecba->ezyx", G, B, B, xe).reshape(self.ne, -1),
+                         np.einsum("xa,yb,zc,ecba->ezyx", B, G, B, xe).reshape(self.ne, -1),
+                         np.einsum("xa,yb,zc,ecba->ezyx", B, B, G, xe).reshape(self.ne, -1)], -1)
+
     def grad(self, x):
         """The physical gradient at the points [ne][nq][3]: J^-T grad_ref = adj(J)^T grad_ref / det J."""
-        B, G, xe = self.B, self.G, self._evec(x)
-        g = np.stack([np.einsum("xa,yb,zc,ecba->ezyx", G, B, B, xe).reshape(self.ne, -1),
-                      np.einsum("xa,yb,zc,ecba->ezyx", B, G, B, xe).reshape(self.ne, -1),
-                      np.einsum("xa,yb,zc,ecba->ezyx", B, B, G, xe).reshape(self.ne, -1)], -1)
-        return np.einsum("eqji,eqj->eqi", self.A, g) / self.detJ[..., None]
+        return np.einsum("eqji,eqj->eqi", self.A, self.ref_grad(x)) / self.detJ[..., None]
 
     def point_values(self, src):
         """f at the quadrature points, [ne][nq]."""
@@ -131,10 +153,11 @@ class LFRef:
         return sigma * np.sum(gp * gp, axis=-1)
 
     # ---- DLFEvalAssemble3D ----
-    def element_vectors(self, f, keep=None):
-        """be[e][nd] = B^T B^T B^T (W f det J), lexicographic; keep (bool [ne]): markers[e] != 0."""
-        Q, B = self.q1d, self.B
-        w = (self.W[None, :] * f * self.detJ).reshape(self.ne, Q, Q, Q)     # [e][qz][qy][qx]
+    def element_vectors(self, f, keep=None, B=None, detJ=None):
+        """be[e][nd] = B^T B^T B^T (W f det J), lexicographic; keep (bool [ne]): markers[e] != 0.
+        (B, detJ: other tables in their place, for the bound.)"""
+        Q, B = self.q1d, self.B if B is None else B
+        w = (self.W[None, :] * f * (self.detJ if detJ is None else detJ)).reshape(self.ne, Q, Q, Q)   # [e][qz][qy][qx]
         u = np.einsum("zc,ezyx->ecyx", B, w)
         u = np.einsum("yb,ecyx->ecbx", B, u)
         be = np.einsum("xa,ecbx->ecba", B, u).reshape(self.ne, -1)
@@ -158,6 +181,72 @@ class LFRef:
             y = self.reduce(self.element_vectors(self.point_values(src), keep))
             b = y if b is None else b + y
         return b if b is not None else np.zeros(self.ndofs, self.dtype)
+
+    # ---- the running bound S of the componentwise criterion (tests/hp_ref.py's rule) ----
+    def geometry_bound(self):
+        """(Aabs [ne][nq][3][3], detabs [ne][nq]): the running magnitudes of adj(J) and det J over Jabs --
+        conv_ref's edge-form bound of the trilinear map (the convex combination of the |edge vectors|), or
+        |J| in Jacobian mode; per cofactor the sum of the magnitudes of its two products
+        (conv_ref.ConvRef._adj), and the first-row expansion of det J over them."""
+        if not hasattr(self, "_gb"):
+            if self.enodes is None:
+                Jabs = np.abs(self.Jm)
+            else:
+                Jabs = conv_ref._edge_jacobians(self.enodes.astype(self.dtype),
+                                                O.gauss_legendre(self.q1d)[0].astype(self.dtype))[1]
+            Aabs = conv_ref.ConvRef._adj(Jabs, self.dtype(1.0))
+            detabs = Jabs[..., 0, 0] * Aabs[..., 0, 0] + Jabs[..., 0, 1] * Aabs[..., 1, 0] + Jabs[..., 0, 2] * Aabs[..., 2, 0]
+            self._gb = (Aabs, detabs)
+        return self._gb
+
+    def _interp_bound(self, x):
+        """sum |B| |x| at the points."""
+        B = np.abs(self.B)
+        xe = np.abs(self._evec(x))
+        return np.einsum("xa,yb,zc,ecba->ezyx", B, B, B, xe).reshape(self.ne, -1)
+
+    def _affine_bound(self, scale, slope, t_ref, T):
+        dt = self.dtype
+        return abs(dt(scale)) * (dt(1.0) + abs(dt(slope)) * (self._interp_bound(T) + abs(dt(t_ref))))
+
+    def point_bound(self, src):
+        """F: the per-point running bound of f, [ne][nq] -- the same expression over the magnitudes of
+        every factor.  JOULE: with g_hat = G phi the reference gradient, Sg_hat = sum |G| |phi| its bound,
+        g = adj^T g_hat / det and Sg_i = sum_r Aabs_ri Sg_hat_r / |det| the bound of the mapped gradient,
+        F = |sigma| sum_i (2 |g_i| Sg_i + u Sg_i^2) + Ssigma |g|^2: the first-order error of a square is
+        twice the value times the error of its argument; the second-order term keeps F positive where
+        the gradient vanishes."""
+        k = src["kind"]
+        dt = self.dtype
+        if k in ("constant", "quad"):
+            return np.abs(self.point_values(src))
+        if k == "gridfunc":
+            return self._interp_bound(src["field"])
+        if k == "affine":
+            return self._affine_bound(src["scale"], src["slope"], src["t_ref"], src["field"])
+        assert k == "joule", k
+        Aabs, _ = self.geometry_bound()
+        Sgh = self.ref_grad(src["phi"], magnitudes=True)
+        Sg = np.einsum("eqji,eqj->eqi", Aabs, Sgh) / np.abs(self.detJ)[..., None]
+        g = np.abs(self.grad(src["phi"]))
+        sigma = np.full(self.detJ.shape, abs(dt(src["sigma"])), dt)
+        Ssigma = sigma
+        if src.get("T") is not None:
+            sigma = np.abs(dt(src["sigma"]) * (dt(1.0) + dt(src["slope"]) * (self.interp(src["T"]) - dt(src["t_ref"]))))
+            Ssigma = self._affine_bound(src["sigma"], src["slope"], src["t_ref"], src["T"])
+        return sigma * np.sum(2 * g * Sg + dt(U) * Sg * Sg, axis=-1) + Ssigma * np.sum(g * g, axis=-1)
+
+    def bound(self, integrators):
+        """S = R^T |B|^T |B|^T |B|^T (W F |det J|) summed over the integrators, |det J| the running
+        magnitude; an excluded element contributes 0 (a dof no kept element touches has S = 0 and must
+        be exactly 0)."""
+        S = np.zeros(self.ndofs, self.dtype)
+        _, detabs = self.geometry_bound()
+        g = self.gm
+        for src, keep in integrators:
+            be = self.element_vectors(self.point_bound(src), keep, B=np.abs(self.B), detJ=detabs)
+            np.add.at(S, np.where(g >= 0, g, -1 - g).ravel(), be.ravel())
+        return S
 
 
 def marker_keep(attr, marker):
