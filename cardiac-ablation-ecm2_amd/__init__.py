@@ -104,6 +104,7 @@ def load_library(path: str = LIB_PATH):
         "ecm2_h1space_info": (i32, [vp, ip, ip, ip]),
         "ecm2_h1space_get_gather_map": (i32, [vp, vp]),
         "ecm2_h1space_boundary_dofs": (i32, [vp, vp, ip]),
+        "ecm2_h1space_essential_dofs": (i32, [vp, vp, i32, vp, ip]),
         "ecm2_h1space_element_order": (i32, [vp, vp]),
         "ecm2_h1space_dof_coords": (i32, [vp, vp, vp]),
         "ecm2_h1space_destroy": (None, [vp]),
@@ -418,6 +419,17 @@ class H1Space:
         return out
 
     GetEssentialTrueDofs = boundary_dofs
+
+    def essential_dofs(self, marker) -> np.ndarray:
+        """FiniteElementSpace::GetEssentialTrueDofs(bdr_attr_is_ess, ...): the sorted, unique dofs of the boundary
+        elements whose attribute a has marker[a - 1] != 0, by the mesh's boundary attributes as they are now."""
+        mk = np.ascontiguousarray(marker, dtype=np.int32)
+        n = ctypes.c_int(0)
+        _check(_lib.ecm2_h1space_essential_dofs(self._h, _np_ptr(mk), int(mk.size), None, ctypes.byref(n)))
+        out = np.empty(n.value, np.int32)
+        if n.value:
+            _check(_lib.ecm2_h1space_essential_dofs(self._h, _np_ptr(mk), int(mk.size), _np_ptr(out), ctypes.byref(n)))
+        return out
 
     def boundary_map(self) -> np.ndarray:
         """Dofs of every boundary element [nbe][(p+1)^2], lexicographic in the quad's frame (xi along
@@ -1010,6 +1022,26 @@ _PAR_SIGS = {
                                             ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                             ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]),
     "ecm2_operator_destroy": (None, [ctypes.c_void_p]),
+    "ecm2_operator_pcg_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                            ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double),
+                                            ctypes.c_void_p, ctypes.c_int]),
+    "ecm2_operator_pcg_prec_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double,
+                                                 ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                                 ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_int]),
+    "ecm2_operator_pcg_mg_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double,
+                                                 ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                                 ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_int]),
+    "ecm2_operator_bicgstab_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double,
+                                                 ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                                 ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_int]),
+    "ecm2_operator_eliminate_rhs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p]),
+    "ecm2_operator_form_linear_system": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "ecm2_linear_form_default_q1d": (ctypes.c_int, [ctypes.c_int]),
     "ecm2_linear_form_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                                ctypes.POINTER(ctypes.c_void_p)]),
@@ -1345,39 +1377,64 @@ class Operator:
     def Mult(self, x, y, stream=None):
         _check(_par_lib().ecm2_operator_mult(self._h, _dev_ptr(x), _dev_ptr(y), _stream(stream)))
 
-    def PCG(self, b, x, ess=None, rel_tol=1e-12, abs_tol=0.0, max_iter=1000, jacobi=True, stream=None, prec=None):
+    def EliminateRHS(self, x, b, ess, stream=None):
+        """ConstrainedOperator::EliminateRHS (linalg/operator.cpp:559-584) on the device: w = 0; w[ess] = x[ess];
+        b -= A w; b[ess] = x[ess].  x, b: 16-byte aligned and distinct; ess: a sorted int32 device list (or None)."""
+        n_ess = 0 if ess is None else int(ess.numel())
+        _check(_par_lib().ecm2_operator_eliminate_rhs(self._h, _dev_ptr(ess) if n_ess else None, n_ess, _dev_ptr(x),
+                                                      _dev_ptr(b), _stream(stream)))
+
+    def FormLinearSystem(self, ess, x, b, copy_interior=False, stream=None):
+        """Operator::FormLinearSystem (linalg/operator.cpp:114-129) for the identity prolongation, in place: unless
+        copy_interior the entries of x off `ess` are zeroed; then EliminateRHS.  x carries the essential values;
+        solve with iterative_mode=True.  RecoverFEMSolution is the identity: x is the solution."""
+        n_ess = 0 if ess is None else int(ess.numel())
+        _check(_par_lib().ecm2_operator_form_linear_system(self._h, _dev_ptr(ess) if n_ess else None, n_ess, _dev_ptr(x),
+                                                           _dev_ptr(b), 1 if copy_interior else 0, _stream(stream)))
+
+    def PCG(self, b, x, ess=None, rel_tol=1e-12, abs_tol=0.0, max_iter=1000, jacobi=True, iterative_mode=False,
+            stream=None, prec=None):
         """ConstrainedOperator(DIAG_ONE) + CGSolver(+OperatorJacobiSmoother); returns (iters, final_norm).
         prec: a ChebyshevSmoother of this operator's size (ecm2_operator_pcg_prec) or a Multigrid whose finest
-        level has it (ecm2_operator_pcg_mg) as CGSolver's preconditioner; `jacobi` is then not read."""
+        level has it (ecm2_operator_pcg_mg) as CGSolver's preconditioner; `jacobi` is then not read.
+        iterative_mode: x is the start, r = b - A~ x (the *_ex entry points); False: x is overwritten."""
         it, nrm = ctypes.c_int(), ctypes.c_double()
         n_ess = 0 if ess is None else int(ess.numel())
+        lib = _par_lib()
+        ex = (1,) if iterative_mode else ()
         if prec is not None:
             if not isinstance(prec, (ChebyshevSmoother, Multigrid)):
                 raise ECM2Error("prec must be a ChebyshevSmoother or a Multigrid")
-            lib = _par_lib()
-            solve = lib.ecm2_operator_pcg_mg if isinstance(prec, Multigrid) else lib.ecm2_operator_pcg_prec
+            if isinstance(prec, Multigrid):
+                solve = lib.ecm2_operator_pcg_mg_ex if iterative_mode else lib.ecm2_operator_pcg_mg
+            else:
+                solve = lib.ecm2_operator_pcg_prec_ex if iterative_mode else lib.ecm2_operator_pcg_prec
             _check(solve(self._h, prec._h, _dev_ptr(ess) if n_ess else None, n_ess, _dev_ptr(b), _dev_ptr(x), rel_tol,
-                         abs_tol, max_iter, ctypes.byref(it), ctypes.byref(nrm), _stream(stream)))
+                         abs_tol, max_iter, ctypes.byref(it), ctypes.byref(nrm), _stream(stream), *ex))
             return it.value, nrm.value
-        _check(_par_lib().ecm2_operator_pcg(self._h, _dev_ptr(ess) if n_ess else None, n_ess, _dev_ptr(b), _dev_ptr(x),
-                                            rel_tol, abs_tol, max_iter, 1 if jacobi else 0,
-                                            ctypes.byref(it), ctypes.byref(nrm), _stream(stream)))
+        solve = lib.ecm2_operator_pcg_ex if iterative_mode else lib.ecm2_operator_pcg
+        _check(solve(self._h, _dev_ptr(ess) if n_ess else None, n_ess, _dev_ptr(b), _dev_ptr(x),
+                     rel_tol, abs_tol, max_iter, 1 if jacobi else 0,
+                     ctypes.byref(it), ctypes.byref(nrm), _stream(stream), *ex))
         return it.value, nrm.value
 
-    def BiCGSTAB(self, b, x, ess=None, rel_tol=1e-12, abs_tol=0.0, max_iter=1000, jacobi_of=None, stream=None):
+    def BiCGSTAB(self, b, x, ess=None, rel_tol=1e-12, abs_tol=0.0, max_iter=1000, jacobi_of=None, stream=None,
+                 iterative_mode=False):
         """ConstrainedOperator(DIAG_ONE) + BiCGSTABSolver (linalg/solvers.cpp:1579-1805) for a nonsymmetric
         operator; jacobi_of: the Operator whose diagonal OperatorJacobiSmoother takes (the symmetric part of a
         form with a ConvectionIntegrator, whose own diagonal is refused), None: no preconditioner.
         Returns (iters, final_norm), final_norm = the last ||s|| or ||r||; bicgstab_last_converged() tells
-        whether it converged."""
+        whether it converged.  iterative_mode: x is the start, r = b - A~ x, r~ = r (ecm2_operator_bicgstab_ex)."""
         it, nrm = ctypes.c_int(), ctypes.c_double()
         n_ess = 0 if ess is None else int(ess.numel())
         if jacobi_of is not None and not isinstance(jacobi_of, Operator):
             raise ECM2Error("jacobi_of must be an Operator")
-        _check(_par_lib().ecm2_operator_bicgstab(self._h, jacobi_of._h if jacobi_of is not None else None,
-                                                 _dev_ptr(ess) if n_ess else None, n_ess, _dev_ptr(b), _dev_ptr(x),
-                                                 rel_tol, abs_tol, max_iter, ctypes.byref(it), ctypes.byref(nrm),
-                                                 _stream(stream)))
+        lib = _par_lib()
+        solve = lib.ecm2_operator_bicgstab_ex if iterative_mode else lib.ecm2_operator_bicgstab
+        _check(solve(self._h, jacobi_of._h if jacobi_of is not None else None,
+                     _dev_ptr(ess) if n_ess else None, n_ess, _dev_ptr(b), _dev_ptr(x),
+                     rel_tol, abs_tol, max_iter, ctypes.byref(it), ctypes.byref(nrm),
+                     _stream(stream), *((1,) if iterative_mode else ())))
         return it.value, nrm.value
 
 

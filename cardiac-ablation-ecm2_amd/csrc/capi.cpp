@@ -24,6 +24,7 @@ struct ecm2_mesh
 struct ecm2_h1space
 {
    ecm2::H1Space s;
+   const ecm2_mesh *m;  // the mesh it was created on (its boundary attributes: ecm2_h1space_essential_dofs)
 };
 struct ecm2_pa_form
 {
@@ -391,7 +392,7 @@ int ecm2_h1space_create(const ecm2_mesh *m, int order, int numbering, ecm2_h1spa
 {
    return guard([&] {
       NEED(m); NEED(out);
-      *out = new ecm2_h1space{ecm2::H1Space::build(m->m, order, numbering)};
+      *out = new ecm2_h1space{ecm2::H1Space::build(m->m, order, numbering), m};
    });
 }
 
@@ -431,6 +432,37 @@ int ecm2_h1space_boundary_dofs(const ecm2_h1space *s, int *out, int *count)
       {
          ECM2_VERIFY(*count >= n, ecm2::ERR_ARG, "boundary dof buffer too small");
          std::memcpy(out, s->s.bdr_dofs.data(), n * sizeof(int));
+      }
+      *count = n;
+   });
+}
+
+// GetEssentialVDofs + MarkerToList (fem/fespace.cpp:548-571, 622-) for a conforming scalar space
+int ecm2_h1space_essential_dofs(const ecm2_h1space *s, const int *bdr_marker, int n_marker, int *out, int *count)
+{
+   return guard([&] {
+      NEED(s); NEED(count);
+      ECM2_VERIFY(n_marker >= 0 && (n_marker == 0 || bdr_marker), ecm2::ERR_ARG, "null argument: bdr_marker");
+      const std::vector<int> &attr = s->m->m.bdr_attr;
+      const size_t nbe = attr.size(), nf = (size_t)(s->s.order + 1) * (s->s.order + 1);
+      ECM2_VERIFY(s->s.bdr_map.size() == nbe * nf, ecm2::ERR_ARG,
+                  "the mesh has " << nbe << " boundary elements, the space's boundary map " << s->s.bdr_map.size() / nf
+                                  << " (refined after the space was created?)");
+      std::vector<char> mark(s->s.ndofs, 0);
+      for (size_t b = 0; b < nbe; b++)
+      {
+         ECM2_VERIFY(attr[b] >= 1 && attr[b] <= n_marker, ecm2::ERR_ARG,
+                     "boundary element " << b << " has attribute " << attr[b] << ", the marker " << n_marker << " entries");
+         if (!bdr_marker[attr[b] - 1]) { continue; }
+         for (size_t i = 0; i < nf; i++) { mark[s->s.bdr_map[b * nf + i]] = 1; }
+      }
+      std::vector<int> list;
+      for (int d = 0; d < s->s.ndofs; d++) { if (mark[d]) { list.push_back(d); } }
+      const int n = (int)list.size();
+      if (out)
+      {
+         ECM2_VERIFY(*count >= n, ecm2::ERR_ARG, "essential dof buffer too small");
+         if (n) { std::memcpy(out, list.data(), n * sizeof(int)); }
       }
       *count = n;
    });
@@ -1115,18 +1147,37 @@ int ecm2_operator_mult(ecm2_operator *op, const double *x, double *y, void *stre
    return guard([&] { NEED(op); NEED(x); NEED(y); op->op->mult(x, y, S(stream)); });
 }
 
-int ecm2_operator_pcg(ecm2_operator *op, const int *ess, int n_ess, const double *b, double *x,
-                      double rel_tol, double abs_tol, int max_iter, int jacobi, int *iterations,
-                      double *final_norm, void *stream)
+int ecm2_operator_pcg_ex(ecm2_operator *op, const int *ess, int n_ess, const double *b, double *x,
+                         double rel_tol, double abs_tol, int max_iter, int jacobi, int *iterations,
+                         double *final_norm, void *stream, int iterative_mode)
 {
    return guard([&] {
       NEED(op); NEED(b); NEED(x);
       g_pcg_converged = 0;
       ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
       const ecm2::PCGResult r = ecm2::pcg_solve(*op->op, ess, n_ess, b, x, rel_tol, abs_tol, max_iter,
-                                                jacobi != 0, S(stream));
+                                                jacobi != 0, S(stream), iterative_mode != 0);
       report(r, iterations, final_norm, g_pcg_converged);
    });
+}
+
+int ecm2_operator_pcg(ecm2_operator *op, const int *ess, int n_ess, const double *b, double *x,
+                      double rel_tol, double abs_tol, int max_iter, int jacobi, int *iterations,
+                      double *final_norm, void *stream)
+{
+   return ecm2_operator_pcg_ex(op, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, jacobi, iterations, final_norm, stream, 0);
+}
+
+// ---- ConstrainedOperator::EliminateRHS, Operator::FormLinearSystem (linalg/operator.cpp:559-584, 114-129) ----
+int ecm2_operator_eliminate_rhs(ecm2_operator *A, const int *ess, int n_ess, const double *x, double *b, void *stream)
+{
+   return guard([&] { NEED(A); ecm2::eliminate_rhs(*A->op, ess, n_ess, x, b, S(stream)); });
+}
+
+int ecm2_operator_form_linear_system(ecm2_operator *A, const int *ess, int n_ess, double *x, double *b,
+                                     int copy_interior, void *stream)
+{
+   return guard([&] { NEED(A); ecm2::form_linear_system(*A->op, ess, n_ess, x, b, copy_interior != 0, S(stream)); });
 }
 
 double ecm2_ode_implicit_coeff(int type)
@@ -1163,12 +1214,20 @@ int ecm2_operator_bicgstab(ecm2_operator *A, ecm2_operator *jacobi_of, const int
                            double *x, double rel_tol, double abs_tol, int max_iter, int *iterations,
                            double *final_norm, void *stream)
 {
+   return ecm2_operator_bicgstab_ex(A, jacobi_of, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, iterations, final_norm,
+                                    stream, 0);
+}
+
+int ecm2_operator_bicgstab_ex(ecm2_operator *A, ecm2_operator *jacobi_of, const int *ess, int n_ess, const double *b,
+                              double *x, double rel_tol, double abs_tol, int max_iter, int *iterations,
+                              double *final_norm, void *stream, int iterative_mode)
+{
    return guard([&] {
       NEED(A); NEED(b); NEED(x);
       g_bicgstab_converged = 0;
       ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
       const ecm2::PCGResult r = ecm2::bicgstab_solve(*A->op, jacobi_of ? jacobi_of->op.get() : nullptr, ess, n_ess, b, x,
-                                                     rel_tol, abs_tol, max_iter, S(stream));
+                                                     rel_tol, abs_tol, max_iter, S(stream), iterative_mode != 0);
       report(r, iterations, final_norm, g_bicgstab_converged);
    });
 }
@@ -1252,12 +1311,19 @@ int ecm2_operator_pcg_prec(ecm2_operator *A, ecm2_smoother *sm, const int *ess, 
                            double rel_tol, double abs_tol, int max_iter, int *iterations, double *final_norm,
                            void *stream)
 {
+   return ecm2_operator_pcg_prec_ex(A, sm, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, iterations, final_norm, stream, 0);
+}
+
+int ecm2_operator_pcg_prec_ex(ecm2_operator *A, ecm2_smoother *sm, const int *ess, int n_ess, const double *b, double *x,
+                              double rel_tol, double abs_tol, int max_iter, int *iterations, double *final_norm,
+                              void *stream, int iterative_mode)
+{
    return guard([&] {
       NEED(A); NEED(sm); NEED(b); NEED(x);
       g_pcg_converged = 0;
       ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
       const ecm2::PCGResult r = ecm2::pcg_solve_prec(*A->op, *sm->sm, ess, n_ess, b, x, rel_tol, abs_tol, max_iter,
-                                                     S(stream));
+                                                     S(stream), iterative_mode != 0);
       report(r, iterations, final_norm, g_pcg_converged);
    });
 }
@@ -1374,11 +1440,19 @@ void ecm2_multigrid_destroy(ecm2_multigrid *mg) { delete mg; }
 int ecm2_operator_pcg_mg(ecm2_operator *A, ecm2_multigrid *mg, const int *ess, int n_ess, const double *b, double *x,
                          double rel_tol, double abs_tol, int max_iter, int *iterations, double *final_norm, void *stream)
 {
+   return ecm2_operator_pcg_mg_ex(A, mg, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, iterations, final_norm, stream, 0);
+}
+
+int ecm2_operator_pcg_mg_ex(ecm2_operator *A, ecm2_multigrid *mg, const int *ess, int n_ess, const double *b, double *x,
+                            double rel_tol, double abs_tol, int max_iter, int *iterations, double *final_norm,
+                            void *stream, int iterative_mode)
+{
    return guard([&] {
       NEED(A); NEED(mg); NEED(b); NEED(x);
       g_pcg_converged = 0;
       ECM2_VERIFY(n_ess == 0 || ess, ecm2::ERR_ARG, "null essential dof list");
-      const ecm2::PCGResult r = ecm2::pcg_solve_mg(*A->op, *mg->mg, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, S(stream));
+      const ecm2::PCGResult r = ecm2::pcg_solve_mg(*A->op, *mg->mg, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, S(stream),
+                                                   iterative_mode != 0);
       report(r, iterations, final_norm, g_pcg_converged);
    });
 }

@@ -8,6 +8,7 @@
 //   pcg_step_r<CHEB>        6 (5 at order 1)    ... t = dinv .* r, z = c_0 t [, r.z]         grid-stride
 //   pcg_update_xd           6 (5 without dinv)  x += alpha d, d = dinv .* r + beta d         flat, a pair per thread
 //   pcg_update_xd_z         5                   x += alpha d, d = z + beta d                 grid-stride
+//   pcg_residual            3                   r = b - ap (iterative_mode's start, once)    flat, a pair per thread
 // The passes that sum park one partial per workgroup in a fixed order (park_partial) for k_dot_final -- no atomics,
 // so two solves are bitwise equal; with a LoopCtl every kernel returns at once when the loop has stopped.
 #include "vec_pass.hpp"
@@ -210,6 +211,15 @@ __global__ void k_pcg_finish_x(int n, const double *__restrict__ alpha, const do
    x[i] = x[i] + *alpha * d[i];
 }
 
+// The start of a solve with iterative_mode = true (CGSolver::Mult, solvers.cpp:875-884; BiCGSTABSolver::Mult,
+// :1618-1627): r = b - ap, ap = A~ x of the caller's x.  Before the loop: no LoopCtl.  A flat grid, a pair per thread.
+__global__ void __launch_bounds__(256)
+k_pcg_residual(int n, const double *__restrict__ b, const double *__restrict__ ap, double *__restrict__ r)
+{
+   const Flat w(n);
+   each_entry(w, n, [&](auto k) { st(r, k, ld(b, k) - ld(ap, k)); });
+}
+
 // ConstrainedOperator around a Mult without a vector copy: saved = v[ess], v[ess] = 0 ...
 __global__ void k_ess_save_zero(int n, const int *__restrict__ idx, double *__restrict__ v,
                                 double *__restrict__ saved)
@@ -313,6 +323,13 @@ void pcg_finish_x(int n, const double *alpha, const double *d, double *x, hipStr
 {
    if (n == 0) { return; }
    hipLaunchKernelGGL(k_pcg_finish_x, dim3(grid_for(n, 256)), dim3(256), 0, s, n, alpha, d, x, ctl);
+   ECM2_HIP(hipGetLastError());
+}
+
+void pcg_residual(int n, const double *b, const double *ap, double *r, hipStream_t s)
+{
+   if (n == 0) { return; }
+   hipLaunchKernelGGL(k_pcg_residual, dim3(grid_for(n / 2 + 1, 256)), dim3(256), 0, s, n, b, ap, r);
    ECM2_HIP(hipGetLastError());
 }
 

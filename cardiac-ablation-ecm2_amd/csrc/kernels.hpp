@@ -3,7 +3,7 @@
 // line / brick p >= 3 apply and the sum-factorised diagonal; k_misc.hip: workgroup-per-element
 // apply, restriction, index and one-thread-per-entry vector kernels; k_lform.hip: the linear form's element vectors;
 // k_bdr.hip: the boundary-face terms; k_conv.hip: the convection term; k_pcg.hip: the deterministic dot and the
-// device PCG's passes; k_bicgstab.hip: the BiCGSTAB loop's vector passes; k_cheb.hip: the Chebyshev smoother's; k_mg.hip: the multigrid cycle's; k_transfer.hip: the
+// device PCG's passes; k_bicgstab.hip: the BiCGSTAB loop's vector passes; k_cheb.hip: the Chebyshev smoother's; k_mg.hip: the multigrid cycle's; k_ess.hip: the essential elimination's; k_transfer.hip: the
 // p-refinement transfer operator, declared in transfer.hpp).
 //
 // Quadrature-data layouts (the qdata a PA form owns):
@@ -669,6 +669,8 @@ void pcg_update_xd(int n, const double *nom, const double *den, const double *be
 void pcg_update_xd_z(int n, const double *nom, const double *den, const double *betanom, double *x, double *d,
                      const double *z, hipStream_t s, const LoopCtl *ctl);
 void pcg_finish_x(int n, const double *alpha, const double *d, double *x, hipStream_t s, const LoopCtl *ctl);
+// r = b - ap (ap = A~ x): the start of a solve with iterative_mode = true, PCG's and BiCGSTAB's; all three 16-byte aligned
+void pcg_residual(int n, const double *b, const double *ap, double *r, hipStream_t s);
 // a stopping test alone (after a distributed dot's all-reduce)
 void pcg_check(const double *v, const PcgStop &stop, hipStream_t s);
 // saved[i] = v[idx[i]], v[idx[i]] = 0  /  v[idx[i]] = y[idx[i]] = saved[i]
@@ -765,6 +767,13 @@ void cheb_power_pass(int n, const double *dinv, const double *h, const double *v
                      hipStream_t s);
 void cheb_scale(int n, const double *norm, double *v, hipStream_t s);
 void cheb_fill_hash(int n, double *v, hipStream_t s);
+
+// ---- kernels of the essential-condition elimination (k_ess.hip) ----
+// ConstrainedOperator::EliminateRHS / Operator::FormLinearSystem (linalg/operator.cpp:559-584, :114-129) beside the
+// Mult, copy_values and gather_idx: b -= z (16-byte aligned); x[idx] = buf, which with gather_idx and a memset of x
+// makes X.SetSubVectorComplement(ess, 0.0).  n == 0: no launch.
+void ess_sub(int n, const double *z, double *b, hipStream_t s);
+void ess_scatter(int n, const int *idx, const double *buf, double *x, hipStream_t s);
 
 // ---- vector kernels of the multigrid cycle (k_mg.hip) ----
 // MultigridBase::SmoothingStep / Cycle (fem/multigrid.cpp:147-232): r = x - h (h = A~ y) in one pass; y += z.

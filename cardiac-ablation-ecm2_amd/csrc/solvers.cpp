@@ -309,13 +309,16 @@ protected:
    ~PcgPrec() = default;
 };
 
-// CGSolver::Mult (solvers.cpp:869-1004) on the constrained A, x overwritten.
+// CGSolver::Mult (solvers.cpp:869-1004) on the constrained A; x overwritten, or with iterative_mode the start.
 PCGResult pcg_loop(LinOp &A, PcgPrec &B, const int *ess, int n_ess, const double *b, double *x, double rel_tol,
-                   double abs_tol, int max_iter, hipStream_t s)
+                   double abs_tol, int max_iter, hipStream_t s, bool iterative_mode)
 {
    // the update passes and k_pcg_finish_x read and write the caller's x two entries at a time; refused here,
    // before anything is allocated or enqueued (the work vectors are allocations of their own)
    ECM2_VERIFY(((uintptr_t)x % 16) == 0, ERR_ARG, "PCG: x must be 16-byte aligned (got " << (const void *)x << ")");
+   // (iterative_mode: the residual pass reads b two entries at a time)
+   ECM2_VERIFY(!iterative_mode || ((uintptr_t)b % 16) == 0, ERR_ARG,
+               "PCG: with iterative_mode b must be 16-byte aligned (got " << (const void *)b << ")");
    const int n = A.size();
    PCGResult res;
    const bool direct = !A.distributed();
@@ -354,8 +357,18 @@ PCGResult pcg_loop(LinOp &A, PcgPrec &B, const int *ess, int n_ess, const double
       }
    };
    B.setup(p);
-   p.copy(p.r, b);
-   if (n) { ECM2_HIP(hipMemsetAsync(x, 0, sizeof(double) * n, s)); }
+   if (iterative_mode)
+   {
+      // r = b - A~ x (solvers.cpp:875-884): the constrained Mult zeroes and restores the essential entries of the
+      // caller's x in place; x is not cleared
+      cmult(x, p.ap);
+      kern::pcg_residual(n, b, p.ap, p.r, s);
+   }
+   else
+   {
+      p.copy(p.r, b);
+      if (n) { ECM2_HIP(hipMemsetAsync(x, 0, sizeof(double) * n, s)); }
+   }
    // d = B r, nom = (d, r) (solvers.cpp:893-903)
    B.first(p);
    kern::dot(n, p.d, p.r, p.partials, p.nom, s, direct ? w.hs_dev : nullptr);
@@ -526,10 +539,10 @@ struct MgPrec final : StoredPrec<Multigrid>
 } // namespace
 
 PCGResult pcg_solve(LinOp &A, const int *ess, int n_ess, const double *b, double *x, double rel_tol,
-                    double abs_tol, int max_iter, bool jacobi, hipStream_t s)
+                    double abs_tol, int max_iter, bool jacobi, hipStream_t s, bool iterative_mode)
 {
    JacobiPrec B(jacobi);
-   return pcg_loop(A, B, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, s);
+   return pcg_loop(A, B, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, s, iterative_mode);
 }
 
 PCGResult pcg_solve(PAForm &A, const int *ess, int n_ess, const double *b, double *x, double rel_tol,
@@ -540,16 +553,16 @@ PCGResult pcg_solve(PAForm &A, const int *ess, int n_ess, const double *b, doubl
 }
 
 PCGResult pcg_solve_prec(LinOp &A, ChebyshevSmoother &S, const int *ess, int n_ess, const double *b, double *x,
-                         double rel_tol, double abs_tol, int max_iter, hipStream_t s)
+                         double rel_tol, double abs_tol, int max_iter, hipStream_t s, bool iterative_mode)
 {
    ECM2_VERIFY(!A.distributed(), ERR_UNSUPPORTED, "PCG with a Chebyshev smoother: distributed operators are not supported");
    ECM2_VERIFY(S.size() == A.size(), ERR_ARG, "PCG: the smoother has size " << S.size() << ", the operator " << A.size());
    ChebPrec B(S);
-   return pcg_loop(A, B, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, s);
+   return pcg_loop(A, B, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, s, iterative_mode);
 }
 
 PCGResult pcg_solve_mg(LinOp &A, Multigrid &M, const int *ess, int n_ess, const double *b, double *x, double rel_tol,
-                       double abs_tol, int max_iter, hipStream_t s)
+                       double abs_tol, int max_iter, hipStream_t s, bool iterative_mode)
 {
    ECM2_VERIFY(!A.distributed(), ERR_UNSUPPORTED, "PCG with a multigrid cycle: distributed operators are not supported");
    ECM2_VERIFY(!A.concatenated(), ERR_UNSUPPORTED,
@@ -557,18 +570,20 @@ PCGResult pcg_solve_mg(LinOp &A, Multigrid &M, const int *ess, int n_ess, const 
    ECM2_VERIFY(M.size() == A.size(), ERR_ARG,
                "PCG: the multigrid's finest level has size " << M.size() << ", the operator " << A.size());
    MgPrec B(M);
-   return pcg_loop(A, B, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, s);
+   return pcg_loop(A, B, ess, n_ess, b, x, rel_tol, abs_tol, max_iter, s, iterative_mode);
 }
 
 // ---------------------------------------------------------------------------------------
 // ConstrainedOperator + BiCGSTABSolver + OperatorJacobiSmoother(second operator)
 // ---------------------------------------------------------------------------------------
 PCGResult bicgstab_solve(LinOp &A, LinOp *jacobi_of, const int *ess, int n_ess, const double *b, double *x,
-                         double rel_tol, double abs_tol, int max_iter, hipStream_t s)
+                         double rel_tol, double abs_tol, int max_iter, hipStream_t s, bool iterative_mode)
 {
    // refused before anything is enqueued: k_bcg_update_xr reads and writes the caller's x two entries at a time
    ECM2_VERIFY(((uintptr_t)x % 16) == 0, ERR_ARG,
                "BiCGSTAB: x must be 16-byte aligned (got " << (const void *)x << ")");
+   ECM2_VERIFY(!iterative_mode || ((uintptr_t)b % 16) == 0, ERR_ARG,
+               "BiCGSTAB: with iterative_mode b must be 16-byte aligned (got " << (const void *)b << ")");
    ECM2_VERIFY(!A.distributed(), ERR_UNSUPPORTED,
                "BiCGSTAB: distributed operators are not supported (no distributed form carries the convection term)");
    const int n = A.size();
@@ -588,8 +603,15 @@ PCGResult bicgstab_solve(LinOp &A, LinOp *jacobi_of, const int *ess, int n_ess, 
    ECM2_HIP(hipMemsetAsync(sc, 0, sizeof(kern::BcgScal), s));
    const ConstrainedMult cmult{A, ess, n_ess, w.saved.data(), s};
    if (jacobi) { jacobi_dinv(*jacobi_of, ess, n_ess, t, dinv, s); }
+   // iterative_mode: r = b - A~ x, r~ = r (solvers.cpp:1618-1622; v is free until the loop's first Mult)
+   if (iterative_mode)
+   {
+      cmult(x, v);
+      kern::pcg_residual(n, b, v, r, s);
+      if (n) { ECM2_HIP(hipMemcpyAsync(rt, r, sizeof(double) * n, hipMemcpyDeviceToDevice, s)); }
+   }
    // x = 0, r = b, r~ = r (solvers.cpp:1623-1628)
-   if (n)
+   else if (n)
    {
       ECM2_HIP(hipMemsetAsync(x, 0, sizeof(double) * n, s));
       ECM2_HIP(hipMemcpyAsync(r, b, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
@@ -900,6 +922,63 @@ void Multigrid::mult(const double *x, double *y, hipStream_t s)
                "multigrid: x and y must be 16-byte aligned (got " << (const void *)x << ", " << (const void *)y << ")");
    ECM2_VERIFY(x != y, ERR_ARG, "multigrid: x and y must be distinct");
    cycle(levels() - 1, x, y, s);
+}
+
+// ---------------------------------------------------------------------------------------
+// ConstrainedOperator::EliminateRHS and Operator::FormLinearSystem (identity prolongation)
+// ---------------------------------------------------------------------------------------
+namespace
+{
+// refused before anything is allocated or enqueued
+void check_elimination_args(const char *what, const int *ess, int n_ess, const double *x, const double *b)
+{
+   ECM2_VERIFY(x && b, ERR_ARG, what << ": null vector");
+   ECM2_VERIFY(n_ess >= 0 && (n_ess == 0 || ess), ERR_ARG, what << ": null essential dof list");
+   ECM2_VERIFY(((uintptr_t)x % 16) == 0 && ((uintptr_t)b % 16) == 0, ERR_ARG,
+               what << ": x and b must be 16-byte aligned (got " << (const void *)x << ", " << (const void *)b << ")");
+   ECM2_VERIFY(x != b, ERR_ARG, what << ": x and b must be distinct");
+}
+
+// w = 0; w[ess] = x[ess]; z = A w; b -= z; b[ess] = x[ess] (operator.cpp:559-584), w and z SolverWork's p and ap.
+// A rank of a distributed operator with no essential dof of its own still takes part: the Mult is collective, and the
+// other ranks' lifted values reach its rows.
+void eliminate(LinOp &A, const int *ess, int n_ess, const double *x, double *b, hipStream_t s)
+{
+   if (n_ess == 0 && !A.distributed()) { return; }
+   const int n = A.size();
+   SolverWork &wk = solver_work();
+   wk.ensure(n, n_ess, false, false, 1);
+   double *w = wk.p.data(), *z = wk.ap.data();
+   if (n) { ECM2_HIP(hipMemsetAsync(w, 0, sizeof(double) * n, s)); }
+   kern::copy_values(n_ess, ess, x, w, s);
+   A.mult(w, z, s);
+   kern::ess_sub(n, z, b, s);
+   kern::copy_values(n_ess, ess, x, b, s);
+   // SolverWork's invariant: no kernel reads its vectors when the next solve starts, on whichever stream
+   ECM2_HIP(hipStreamSynchronize(s));
+}
+} // namespace
+
+void eliminate_rhs(LinOp &A, const int *ess, int n_ess, const double *x, double *b, hipStream_t s)
+{
+   check_elimination_args("EliminateRHS", ess, n_ess, x, b);
+   eliminate(A, ess, n_ess, x, b, s);
+}
+
+void form_linear_system(LinOp &A, const int *ess, int n_ess, double *x, double *b, bool copy_interior, hipStream_t s)
+{
+   check_elimination_args("FormLinearSystem", ess, n_ess, x, b);
+   const int n = A.size();
+   if (!copy_interior && n)
+   {
+      // X.SetSubVectorComplement(ess, 0.0): the essential entries parked on SolverWork's saved around a memset
+      SolverWork &wk = solver_work();
+      wk.ensure(n, n_ess, false, false, 1);
+      kern::gather_idx(n_ess, ess, x, wk.saved.data(), s);
+      ECM2_HIP(hipMemsetAsync(x, 0, sizeof(double) * n, s));
+      kern::ess_scatter(n_ess, ess, wk.saved.data(), x, s);
+   }
+   eliminate(A, ess, n_ess, x, b, s);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -6,6 +6,9 @@
 // Reference:
 //   Operator (the solver-facing interface)     linalg/operator.hpp:24-110
 //   ConstrainedOperator DIAG_ONE               linalg/operator.cpp:586-646
+//   ConstrainedOperator::EliminateRHS          linalg/operator.cpp:559-584
+//   Operator::FormLinearSystem                 linalg/operator.cpp:114-129
+//   IterativeSolver::iterative_mode            linalg/solvers.cpp:29-30, 875-884, 1618-1627
 //   CGSolver::Mult                             linalg/solvers.cpp:869-1004
 //   BiCGSTABSolver::Mult                       linalg/solvers.cpp:1579-1805
 //   OperatorJacobiSmoother (PA diagonal)       linalg/solvers.hpp:421, bilinearform_ext.cpp:370-454
@@ -133,8 +136,14 @@ struct PCGResult
 // Scalars stay on the device and so do the stopping tests: the loop is driven by the device (kernels.hpp
 // LoopCtl), the host polls a mapped mirror's progress mark and synchronises the stream for the two read-backs
 // before the loop and once after it.
+// iterative_mode (IterativeSolver's default in the reference, solvers.cpp:29-30; here off unless asked for): x is the
+// start, r = b - A~ x (CGSolver::Mult, solvers.cpp:875-884) by the constrained Mult on the caller's x and one
+// 16-byte pass; everything after that is the same loop.  b must then be 16-byte aligned too (ERR_ARG).  With
+// b[ess] = x[ess] (form_linear_system) r[ess] = 0 exactly and x[ess] keeps its bits.  The preconditioners stay
+// iterative_mode = false (solvers.cpp:181).  false: the launches of before, not one more.
 PCGResult pcg_solve(LinOp &A, const int *ess_dev, int n_ess, const double *b, double *x,
-                    double rel_tol, double abs_tol, int max_iter, bool jacobi, hipStream_t s);
+                    double rel_tol, double abs_tol, int max_iter, bool jacobi, hipStream_t s,
+                    bool iterative_mode = false);
 PCGResult pcg_solve(PAForm &A, const int *ess_dev, int n_ess, const double *b, double *x,
                     double rel_tol, double abs_tol, int max_iter, bool jacobi, hipStream_t s);
 
@@ -149,8 +158,9 @@ PCGResult pcg_solve(PAForm &A, const int *ess_dev, int n_ess, const double *b, d
 // dinv = 1 / diag(jacobi_of), essential rows 1 -- as a caller builds it from the symmetric part, since the
 // diagonal of a form with an active convection integrator is refused.
 // A distributed operator (distributed() == true): ERR_UNSUPPORTED.  x must be 16-byte aligned (ERR_ARG).
+// iterative_mode: r = b - A~ x, r~ = r (solvers.cpp:1618-1622), as pcg_solve's; nothing else changes.
 PCGResult bicgstab_solve(LinOp &A, LinOp *jacobi_of, const int *ess_dev, int n_ess, const double *b, double *x,
-                         double rel_tol, double abs_tol, int max_iter, hipStream_t s);
+                         double rel_tol, double abs_tol, int max_iter, hipStream_t s, bool iterative_mode = false);
 
 // PowerMethod::EstimateLargestEigenvalue (linalg/operator.cpp:871-928) on D^-1 A~, A~ the DIAG_ONE constrained A
 // and dinv a device vector (1 / diag, essential rows 1): each step normalises v0 (v0 *= 1 / sqrt((v0, v0))),
@@ -219,7 +229,7 @@ private:
 // allocated or enqueued: distributed operators (ERR_UNSUPPORTED), B not of A's size (ERR_ARG), x not 16-byte
 // aligned (ERR_ARG, the loop's own check).
 PCGResult pcg_solve_prec(LinOp &A, ChebyshevSmoother &B, const int *ess_dev, int n_ess, const double *b, double *x,
-                         double rel_tol, double abs_tol, int max_iter, hipStream_t s);
+                         double rel_tol, double abs_tol, int max_iter, hipStream_t s, bool iterative_mode = false);
 
 // Multigrid / MultigridBase (fem/multigrid.cpp:106-232: Mult, SmoothingStep, Cycle), V-cycle only, over levels 0
 // (coarsest) .. L - 1 that the caller supplies: each level's operator, its ChebyshevSmoother (built by the caller
@@ -280,7 +290,20 @@ private:
 // before anything is allocated or enqueued: distributed operators and a loopback group as A (ERR_UNSUPPORTED), B not
 // of A's size (ERR_ARG), x not 16-byte aligned (ERR_ARG, the loop's own check).
 PCGResult pcg_solve_mg(LinOp &A, Multigrid &B, const int *ess_dev, int n_ess, const double *b, double *x, double rel_tol,
-                       double abs_tol, int max_iter, hipStream_t s);
+                       double abs_tol, int max_iter, hipStream_t s, bool iterative_mode = false);
+
+// ConstrainedOperator::EliminateRHS (linalg/operator.cpp:559-584) per entry: w = 0; w[ess] = x[ess]; z = A w; b -= z;
+// b[ess] = x[ess].  Any LinOp: the serial form, a loopback group in its concatenated numbering, an RCCL rank or a
+// member (the Mult is collective; no dot is needed).  w and z are the solvers' workspace (its p and ap: nothing is
+// allocated after the first call of a size) and the call ends with the stream synchronised, as every solve does.
+// n_ess == 0 on an operator that does not communicate: b keeps its bits and no kernel is launched.  x, b: device
+// vectors of A.size(), 16-byte aligned and distinct (ERR_ARG otherwise, before anything is enqueued).
+void eliminate_rhs(LinOp &A, const int *ess_dev, int n_ess, const double *x, double *b, hipStream_t s);
+// Operator::FormLinearSystem (linalg/operator.cpp:114-129) for the identity prolongation (X = x, B = b in place):
+// unless copy_interior, X.SetSubVectorComplement(ess, 0.0) (the essential entries gathered, x cleared, scattered
+// back); then eliminate_rhs.  RecoverFEMSolution is the identity.
+void form_linear_system(LinOp &A, const int *ess_dev, int n_ess, double *x, double *b, bool copy_interior,
+                        hipStream_t s);
 
 // ODESolver::SelectImplicit numbering (ode.cpp:77-91): 21 BackwardEuler, 22 SDIRK23(L-stable),
 // 23 SDIRK33, 32 ImplicitMidpoint, 33 SDIRK23 (A-stable, order 3), 34 SDIRK34.

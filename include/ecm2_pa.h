@@ -194,6 +194,13 @@ int ecm2_h1space_get_gather_map(const ecm2_h1space *s, int *out /* host [ne][nd]
  * a PA form without an explicit order derives the same order at assemble. */
 int ecm2_h1space_element_order(const ecm2_h1space *s, int *perm);
 int ecm2_h1space_boundary_dofs(const ecm2_h1space *s, int *out, int *count);
+/* FiniteElementSpace::GetEssentialTrueDofs(bdr_attr_is_ess, ...) (fem/fespace.cpp:548-571 GetEssentialVDofs,
+ * :622- MarkerToList) for a conforming scalar space: the sorted, unique dofs of the boundary elements whose
+ * attribute a has bdr_marker[a - 1] != 0 (host [n_marker]), from the space's boundary map and the boundary
+ * attributes of its mesh as they are at the call (the space refers to the mesh it was created on, which must
+ * be alive and not refined since).  Two-call pattern, as ecm2_h1space_boundary_dofs.  A boundary attribute above
+ * n_marker: ECM2_ERR_ARG.  An all-ones marker gives what ecm2_h1space_boundary_dofs gives. */
+int ecm2_h1space_essential_dofs(const ecm2_h1space *s, const int *bdr_marker, int n_marker, int *out, int *count);
 int ecm2_h1space_dof_coords(const ecm2_h1space *s, const ecm2_mesh *m, double *out /* host [ndofs][3] */);
 /* The dofs of every boundary element, host out[nbe][(order+1)^2], lexicographic in the quad's own
  * frame (see ecm2_mesh_get_boundary_nodes), taken from the adjacent element's row of the gather
@@ -448,6 +455,32 @@ int ecm2_operator_mult(ecm2_operator *op, const double *x, double *y, void *stre
 int ecm2_operator_pcg(ecm2_operator *op, const int *ess, int n_ess, const double *b, double *x,
                       double rel_tol, double abs_tol, int max_iter, int jacobi, int *iterations,
                       double *final_norm, void *stream);
+/* ecm2_operator_pcg with IterativeSolver::iterative_mode (linalg/solvers.cpp:29-30: the reference's default is
+ * true; ecm2_operator_pcg is this function with 0).  iterative_mode != 0: x is the start and is not cleared,
+ * r = b - A~ x (CGSolver::Mult, solvers.cpp:875-884) by the constrained Mult, which zeroes and restores the
+ * essential entries of x in place, and one 16-byte pass; b must then be 16-byte aligned too (ECM2_ERR_ARG).
+ * Every stop, read-back and result after that is ecm2_operator_pcg's.  With b[ess] = x[ess], as
+ * ecm2_operator_form_linear_system leaves them, r[ess] = 0 exactly and x[ess] keeps its bits.  The
+ * preconditioner stays iterative_mode = false (solvers.cpp:181).  Every operator ecm2_operator_pcg accepts. */
+int ecm2_operator_pcg_ex(ecm2_operator *op, const int *ess, int n_ess, const double *b, double *x,
+                         double rel_tol, double abs_tol, int max_iter, int jacobi, int *iterations,
+                         double *final_norm, void *stream, int iterative_mode);
+/* ConstrainedOperator::EliminateRHS (linalg/operator.cpp:559-584), per entry: w = 0; w[ess] = x[ess]; z = A w;
+ * b -= z; b[ess] = x[ess].  ess: device int [n_ess], sorted and unique; x, b: device vectors of the operator's
+ * size, 16-byte aligned and distinct (ECM2_ERR_ARG otherwise, before anything is enqueued).  Any operator: the
+ * serial form, a loopback group in its concatenated numbering, an RCCL rank or a member (the Mult is collective:
+ * every rank calls it, one without essential dofs too).  w and z are the solvers' work vectors: nothing is
+ * allocated after the first call of a size.  n_ess == 0 on an operator that does not communicate leaves b
+ * bitwise unchanged and launches no kernel.  Returns with the stream synchronised. */
+int ecm2_operator_eliminate_rhs(ecm2_operator *A, const int *ess, int n_ess, const double *x, double *b,
+                                void *stream);
+/* Operator::FormLinearSystem (linalg/operator.cpp:114-129) for the identity prolongation, in place (X = x,
+ * B = b): with copy_interior == 0 the entries of x off the list are set to zero first
+ * (X.SetSubVectorComplement(ess, 0.0)); then ecm2_operator_eliminate_rhs.  x carries the essential values in
+ * and out; solve with iterative_mode = 1 (or 0: the solvers keep x[ess] = b[ess]).  Operator::RecoverFEMSolution
+ * (operator.cpp:148-161) is the identity here: x is the solution. */
+int ecm2_operator_form_linear_system(ecm2_operator *A, const int *ess, int n_ess, double *x, double *b,
+                                     int copy_interior, void *stream);
 /* ODESolver::SelectImplicit types (ode.cpp:77-91): 21 BackwardEuler, 22 SDIRK23 (L-stable),
  * 23 SDIRK33, 32 ImplicitMidpoint, 33 SDIRK23 (A-stable), 34 SDIRK34.  Returns the stage
  * coefficient c (every stage solves (M + c*dt*K) k = -K u_stage), 0 for unknown types. */
@@ -486,6 +519,12 @@ int ecm2_ode_step_source(int type, ecm2_operator *T, ecm2_operator *K, const dou
 int ecm2_operator_bicgstab(ecm2_operator *A, ecm2_operator *jacobi_of /* NULL: none */, const int *ess, int n_ess,
                            const double *b, double *x, double rel_tol, double abs_tol, int max_iter,
                            int *iterations, double *final_norm, void *stream);
+/* ecm2_operator_bicgstab with iterative_mode (ecm2_operator_bicgstab is this function with 0): != 0 starts from
+ * the caller's x, r = b - A~ x, r~ = r (BiCGSTABSolver::Mult, linalg/solvers.cpp:1618-1622); b must then be
+ * 16-byte aligned too (ECM2_ERR_ARG).  Nothing else changes. */
+int ecm2_operator_bicgstab_ex(ecm2_operator *A, ecm2_operator *jacobi_of /* NULL: none */, const int *ess, int n_ess,
+                              const double *b, double *x, double rel_tol, double abs_tol, int max_iter,
+                              int *iterations, double *final_norm, void *stream, int iterative_mode);
 /* IterativeSolver::GetConverged() of the calling thread's last ecm2_operator_bicgstab (BiCGSTABSolver,
  * linalg/solvers.cpp:1579-1805): 1 converged, 0 not (or no solve yet); per calling thread, as
  * ecm2_pcg_last_converged. */
@@ -543,6 +582,11 @@ int ecm2_power_method(ecm2_operator *A, ecm2_operator *diag_of /* NULL: A */, co
 int ecm2_operator_pcg_prec(ecm2_operator *A, ecm2_smoother *sm, const int *ess, int n_ess, const double *b, double *x,
                            double rel_tol, double abs_tol, int max_iter, int *iterations, double *final_norm,
                            void *stream);
+/* ecm2_operator_pcg_prec with iterative_mode, as ecm2_operator_pcg_ex (CGSolver::Mult, solvers.cpp:875-884): the
+ * outer CG starts from x; the smoother itself stays iterative_mode = false (solvers.cpp:181).  0: that function. */
+int ecm2_operator_pcg_prec_ex(ecm2_operator *A, ecm2_smoother *sm, const int *ess, int n_ess, const double *b,
+                              double *x, double rel_tol, double abs_tol, int max_iter, int *iterations,
+                              double *final_norm, void *stream, int iterative_mode);
 /* ecm2_ode_step_source whose stage solves run ecm2_operator_pcg_prec with sm, a smoother built from T (fixed
  * over the step, so one smoother serves every stage; CGSolver::Mult solvers.cpp:869-1004 with
  * OperatorChebyshevSmoother::Mult solvers.cpp:619-658).  b == NULL: no source. */
@@ -615,6 +659,11 @@ void ecm2_multigrid_destroy(ecm2_multigrid *mg);
 int ecm2_operator_pcg_mg(ecm2_operator *A, ecm2_multigrid *mg, const int *ess, int n_ess, const double *b, double *x,
                          double rel_tol, double abs_tol, int max_iter, int *iterations, double *final_norm,
                          void *stream);
+/* ecm2_operator_pcg_mg with iterative_mode, as ecm2_operator_pcg_ex (CGSolver::Mult, solvers.cpp:875-884): the
+ * outer CG starts from x; every cycle still starts from a zero guess (fem/multigrid.cpp:106-118).  0: that function. */
+int ecm2_operator_pcg_mg_ex(ecm2_operator *A, ecm2_multigrid *mg, const int *ess, int n_ess, const double *b,
+                            double *x, double rel_tol, double abs_tol, int max_iter, int *iterations,
+                            double *final_norm, void *stream, int iterative_mode);
 void ecm2_operator_destroy(ecm2_operator *op);
 
 /* ------------------------------------------------------------------------ */
