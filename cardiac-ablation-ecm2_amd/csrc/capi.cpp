@@ -11,7 +11,6 @@
 #include "partition.hpp"
 #include "solvers.hpp"
 #include "transfer.hpp"
-#include "htransfer.hpp"
 
 #include <cstring>
 #include <memory>
@@ -48,7 +47,7 @@ struct ecm2_smoother
 };
 struct ecm2_transfer
 {
-   std::unique_ptr<ecm2::Transfer> t;
+   ecm2::Transfer t;
 };
 struct ecm2_multigrid
 {
@@ -1348,8 +1347,7 @@ int ecm2_transfer_create(int ne, int order_lo, int ndofs_lo, const int *gather_l
    return guard([&] {
       NEED(out);
       *out = nullptr;
-      *out = new ecm2_transfer{std::unique_ptr<ecm2::Transfer>(
-         new ecm2::PTransfer(ne, order_lo, ndofs_lo, gather_lo, order_hi, ndofs_hi, gather_hi))};
+      *out = new ecm2_transfer{ecm2::Transfer::p_refinement(ne, order_lo, ndofs_lo, gather_lo, order_hi, ndofs_hi, gather_hi)};
    });
 }
 
@@ -1361,19 +1359,19 @@ int ecm2_transfer_create_h(int order, int ne_lo, int ndofs_lo, const int *gather
    return guard([&] {
       NEED(out);
       *out = nullptr;
-      *out = new ecm2_transfer{std::unique_ptr<ecm2::Transfer>(
-         new ecm2::HTransfer(order, ne_lo, ndofs_lo, gather_lo, ne_hi, ndofs_hi, gather_hi, parent, octant))};
+      *out = new ecm2_transfer{
+         ecm2::Transfer::h_refinement(order, ne_lo, ndofs_lo, gather_lo, ne_hi, ndofs_hi, gather_hi, parent, octant)};
    });
 }
 
 int ecm2_transfer_mult(ecm2_transfer *t, const double *x_lo, double *y_hi, void *stream)
 {
-   return guard([&] { NEED(t); NEED(x_lo); NEED(y_hi); t->t->mult(x_lo, y_hi, S(stream)); });
+   return guard([&] { NEED(t); NEED(x_lo); NEED(y_hi); t->t.mult(x_lo, y_hi, S(stream)); });
 }
 
 int ecm2_transfer_mult_transpose(ecm2_transfer *t, const double *x_hi, double *y_lo, void *stream)
 {
-   return guard([&] { NEED(t); NEED(x_hi); NEED(y_lo); t->t->mult_transpose(x_hi, y_lo, S(stream)); });
+   return guard([&] { NEED(t); NEED(x_hi); NEED(y_lo); t->t.mult_transpose(x_hi, y_lo, S(stream)); });
 }
 
 int ecm2_transfer_info(const ecm2_transfer *t, int *ne, int *order_lo, int *order_hi, int *ndofs_lo, int *ndofs_hi,
@@ -1381,12 +1379,12 @@ int ecm2_transfer_info(const ecm2_transfer *t, int *ne, int *order_lo, int *orde
 {
    return guard([&] {
       NEED(t);
-      if (ne) { *ne = t->t->ne(); }
-      if (order_lo) { *order_lo = t->t->order_lo(); }
-      if (order_hi) { *order_hi = t->t->order_hi(); }
-      if (ndofs_lo) { *ndofs_lo = t->t->width(); }
-      if (ndofs_hi) { *ndofs_hi = t->t->height(); }
-      if (plan_bytes) { *plan_bytes = (long)t->t->plan_bytes(); }
+      if (ne) { *ne = t->t.ne(); }
+      if (order_lo) { *order_lo = t->t.order_lo(); }
+      if (order_hi) { *order_hi = t->t.order_hi(); }
+      if (ndofs_lo) { *ndofs_lo = t->t.width(); }
+      if (ndofs_hi) { *ndofs_hi = t->t.height(); }
+      if (plan_bytes) { *plan_bytes = (long)t->t.plan_bytes(); }
    });
 }
 
@@ -1418,7 +1416,7 @@ int ecm2_multigrid_create(int nlevels, ecm2_operator *const *ops, ecm2_smoother 
          if (k + 1 < nlevels)
          {
             NEED(transfers[k]);
-            tr.push_back(transfers[k]->t.get());
+            tr.push_back(&transfers[k]->t);
          }
       }
       *out = new ecm2_multigrid{std::unique_ptr<ecm2::Multigrid>(new ecm2::Multigrid(o, sm, tr, e, ne, pre, post, nullptr))};

@@ -234,8 +234,8 @@ PCGResult pcg_solve_prec(LinOp &A, ChebyshevSmoother &B, const int *ess_dev, int
 // Multigrid / MultigridBase (fem/multigrid.cpp:106-232: Mult, SmoothingStep, Cycle), V-cycle only, over levels 0
 // (coarsest) .. L - 1 that the caller supplies: each level's operator, its ChebyshevSmoother (built by the caller
 // on that level's operator and essential list), its essential list (device, copied) and the transfer k -> k + 1
-// (a Transfer, transfer.hpp: a PTransfer between two orders, an HTransfer between a mesh and its refinement, mixed freely).  The essential
-// rows and columns of the prolongations are removed as GeometricMultigrid does (fem/multigrid.cpp:296-309,
+// (a Transfer, transfer.hpp: one class for both kinds, between two orders on one mesh or between a mesh and its
+// refinement, mixed freely).  The essential rows and columns of the prolongations are removed as GeometricMultigrid does (fem/multigrid.cpp:296-309,
 // RectangularConstrainedOperator): the coarse essential entries of the input and the fine essential entries of
 // the output are zero, and likewise for the transpose.
 // mult(x, y): one cycle from a zero guess (iterative_mode is not used), the reference's operations per entry:

@@ -11,13 +11,13 @@ refined meshes' element order (child k of element i at 8 i + k) -- not section 4
 Jacobi-PCG and p-only cycles are therefore timed on the same finest space.  Solvers: "jacobi"; "p_vcycle_pcg" (the
 levels of the finest mesh, ex26's coarse PCG (1e-2, 200): section 4f's form); "p_vcycle_smoother" (the same levels,
 the coarsest smoothed once); "hp_vcycle" (all levels, the coarsest smoothed once).  Then the two h-transfer kernels
-alone at the (n/2, 1) -> (n, 1) pair: ms per call (20 calls, the median of 5) and the bytes that must move (both
-vectors, both maps, the owner words, the children table; the restriction also its coarse E-vector written and read
-and the transposed map).  Reported, not gated.  One MI355X; one JSON line per shape.
+alone at the (n/2, 1) -> (n, 1) pair (profiles/transfer_cost.py's transfer_times): ms per call and the bytes that
+must move.  Reported, not gated.  One MI355X; one JSON line per shape.
 
 Usage: python profiles/hmg_cost.py [c4|c5|all] [reps = 3] [n0 (overrides the coarsest mesh's elements per side)]
        python profiles/hmg_cost.py kernels [n0]     (the two kernels at the C4 pair alone: what a rocprofv3
-                                                     --kernel-trace --stats run wraps)"""
+                                                     --kernel-trace --stats run wraps)
+       --lib=path times another build of the library"""
 import json
 import os
 import statistics
@@ -29,21 +29,11 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from __graft_entry__ import _load_pkg  # noqa: E402
+from transfer_cost import load, timed_call, transfer_times  # noqa: E402
 
 REL_TOL = 1e-10
 EX26_COARSE = (1e-2, 200)
 SHAPES = {"c4": (27, 2, (2,)), "c5": (17, 2, (2, 4))}   # n0, refinements, the orders above p = 1 on the finest mesh
-
-
-def timed_call(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    out = fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1), out
 
 
 def hierarchy(E, n0, refinements):
@@ -53,27 +43,6 @@ def hierarchy(E, n0, refinements):
         m.UniformRefinement()
         meshes.append(m)
     return meshes
-
-
-def kernel_times(E, lo, hi, res):
-    """The two h-transfer kernels alone between the spaces lo and hi."""
-    T = E.HRefinementTransfer(lo, hi)
-    xc = torch.rand(lo.ndofs, dtype=torch.float64, device="cuda")
-    xf = torch.rand(hi.ndofs, dtype=torch.float64, device="cuda")
-    yc, yf = torch.empty_like(xc), torch.empty_like(xf)
-    calls = {"prolong_ms": lambda: T.Mult(xc, yf), "restrict_ms": lambda: T.MultTranspose(xf, yc)}
-    for key, fn in calls.items():
-        for _ in range(3):
-            fn()
-        res[key] = round(statistics.median(timed_call(lambda: [fn() for _ in range(20)])[0] / 20 for _ in range(5)), 5)
-    nd = lo.nd
-    maps = 4 * nd * (lo.ne + hi.ne)
-    owner, children, csr = 16 * hi.ne, 32 * lo.ne, 4 * (lo.ndofs + 1) + 4 * nd * lo.ne
-    res["pair"] = {"elements": [lo.ne, hi.ne], "ndofs": [lo.ndofs, hi.ndofs], "order": lo.order, "plan_bytes": T.plan_bytes}
-    res["prolong_bytes"] = 8 * (lo.ndofs + hi.ndofs) + maps + owner + children
-    res["restrict_bytes"] = 8 * (lo.ndofs + hi.ndofs) + 4 * nd * hi.ne + owner + children + 2 * 8 * nd * lo.ne + csr
-    res["prolong_tb_s"] = round(res["prolong_bytes"] / res["prolong_ms"] * 1e-9, 3)
-    res["restrict_tb_s"] = round(res["restrict_bytes"] / res["restrict_ms"] * 1e-9, 3)
 
 
 def run(E, shape, reps, n0_override):
@@ -130,7 +99,7 @@ def run(E, shape, reps, n0_override):
     res["x_against_jacobi"] = {k: float((v - xs["jacobi"]).abs().max()) / top_x for k, v in xs.items() if k != "jacobi"}
     jac = res["solvers"]["jacobi"]["solve_ms"]
     res["solve_time_against_jacobi"] = {k: round(v["solve_ms"] / jac, 4) for k, v in res["solvers"].items()}
-    kernel_times(E, spaces[nh - 1], spaces[nh], res)
+    transfer_times(tr[nh - 1], spaces[nh - 1], spaces[nh], res)
     res["device"] = torch.cuda.get_device_name(0)
     print(json.dumps(res), flush=True)
 
@@ -138,15 +107,15 @@ def run(E, shape, reps, n0_override):
 def kernels_only(E, n0):
     meshes = hierarchy(E, n0, 1)
     res = {"shape": "kernels"}
-    kernel_times(E, E.H1Space(meshes[0], 1), E.H1Space(meshes[1], 1), res)
+    lo, hi = E.H1Space(meshes[0], 1), E.H1Space(meshes[1], 1)
+    transfer_times(E.HRefinementTransfer(lo, hi), lo, hi, res)
     print(json.dumps(res), flush=True)
 
 
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     which = args[0] if args else "all"
-    E = _load_pkg()
-    E.load_library()
+    E = load(sys.argv[1:])
     if which == "kernels":
         return kernels_only(E, int(args[1]) if len(args) > 1 else 54)
     reps = int(args[1]) if len(args) > 1 else 3

@@ -8,9 +8,10 @@ Each solver -- Jacobi-PCG (the baseline: the same run's untouched path), the V-c
 smoother as the coarse solve and with ex26's coarse PCG (1e-2, 200) -- after a warm-up solve, three repetitions,
 HIP events around each call; recorded: iterations, ms per solve (median and the three values), ms per iteration.
 The set-up (forms aside: the smoothers' diagonals and power steps, the transfer plans) is timed beside them, and
-each transfer direction and the fine Mult alone (20 calls).  Reported, not gated.  One MI355X; one JSON line per solve.
+each transfer direction (profiles/transfer_cost.py's transfer_times) and the fine Mult alone (20 calls).  Reported,
+not gated.  One MI355X; one JSON line per solve.
 
-Usage: python profiles/mg_cost.py [c4|c5|all] [reps = 3] [n (overrides the shape's elements per side)]"""
+Usage: python profiles/mg_cost.py [c4|c5|all] [reps = 3] [n (overrides the shape's elements per side)] [--lib=path]"""
 import json
 import os
 import statistics
@@ -22,21 +23,11 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from __graft_entry__ import _load_pkg  # noqa: E402
+from transfer_cost import call_ms, load, timed_call, transfer_times  # noqa: E402
 
 REL_TOL = 1e-10
 EX26_COARSE = (1e-2, 200)
 SHAPES = {"c4": (108, (1, 2), ("k", "mk")), "c5": (68, (1, 2, 4), ("k",))}
-
-
-def timed_call(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    out = fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1), out
 
 
 def run(E, shape, reps, n_override):
@@ -92,20 +83,11 @@ def run(E, shape, reps, n_override):
         res["x_against_jacobi"] = {k: float((v - xs["jacobi"]).abs().max()) / top for k, v in xs.items() if k != "jacobi"}
         jac = res["solvers"]["jacobi"]["solve_ms"]
         res["solve_time_against_jacobi"] = {k: round(v["solve_ms"] / jac, 4) for k, v in res["solvers"].items()}
-        # the transfer's two directions and the fine Mult alone (the rocprofv3 run reads the same calls per kernel)
-        xc = torch.rand(spaces[-2].ndofs, dtype=torch.float64, device="cuda")
-        yc, yf = torch.empty_like(xc), torch.empty_like(b)
-        T = tr[-1]
-        calls = {"prolong_ms": lambda: T.Mult(xc, yf), "restrict_ms": lambda: T.MultTranspose(b, yc),
-                 "mult_ms": lambda: A.Mult(b, yf)}
-        for key, fn in calls.items():
-            for _ in range(3):
-                fn()
-            res[key] = round(statistics.median(timed_call(lambda: [fn() for _ in range(20)])[0] / 20 for _ in range(5)), 5)
-        must = 8 * (spaces[-2].ndofs + nd) + T.plan_bytes
-        res["transfer_bytes"] = must
-        res["prolong_tb_s"] = round(must / res["prolong_ms"] * 1e-9, 3)
-        res["restrict_tb_s"] = round(must / res["restrict_ms"] * 1e-9, 3)
+        # the transfer's two directions (profiles/transfer_cost.py) and the fine Mult alone at the finest pair (the
+        # rocprofv3 run reads the same calls per kernel)
+        transfer_times(tr[-1], spaces[-2], spaces[-1], res)
+        yf = torch.empty_like(b)
+        res["mult_ms"] = call_ms(lambda: A.Mult(b, yf))
         res["device"] = torch.cuda.get_device_name(0)
         print(json.dumps(res), flush=True)
         del solvers, sm, tr, ops, xs
@@ -116,8 +98,7 @@ def main():
     which = args[0] if args else "all"
     reps = int(args[1]) if len(args) > 1 else 3
     n_override = int(args[2]) if len(args) > 2 else 0
-    E = _load_pkg()
-    E.load_library()
+    E = load(sys.argv[1:])
     for shape in (("c4", "c5") if which == "all" else (which,)):
         run(E, shape, reps, n_override)
 

@@ -1,5 +1,5 @@
 """GPU tests of the device h-refinement transfer operator (HRefinementTransfer / ecm2_transfer_create_h:
-FiniteElementSpace::RefinementOperator, fem/fespace.cpp:1833-2120, in the kernels of csrc/k_htransfer.hip) against
+FiniteElementSpace::RefinementOperator, fem/fespace.cpp:1833-2120, in the kernels of csrc/k_transfer.hip) against
 the 80-bit evaluation of tests/hmg_ref.py, componentwise: |y_i - y_80bit,i| <= C_HXFER u S_i with S = |P| |x| and
 |P|^T |x| (C_HXFER measured by tests/test_hmg_reference.py).  Every output is preset to NaN, so an entry that is not
 written fails; every result is computed twice and must be bitwise equal."""

@@ -16,7 +16,7 @@ import hp_ref as HP
 import mg_cases as MC
 
 ORDERS = (1, 2, 3, 4)
-# the smallest nonzero magnitude in the 1D tables (htransfer.hpp's argument for thresholding them)
+# the smallest nonzero magnitude in the 1D tables (transfer.hpp's argument for thresholding them)
 MIN_NONZERO = {1: 0.5, 2: 0.125, 3: 0.0559, 4: 0.0319}
 # the largest spread of x after six iterations and of one cycle's y (relative to the max) under the three summation
 # orders, as measured

@@ -1,6 +1,6 @@
-"""CPU test of the h-refinement transfer operator's host construction (csrc/htransfer.cpp): builds
-tests/cpp/htransfer_plan_check.cpp with that source, fe.cpp and mesh.cpp under ASan + UBSan (the library Makefile's
-htransfer_plan_check target; the sanitizers are linked into that program only) and runs it as a child process on
+"""CPU test of the h-refinement transfer operator's host construction (csrc/transfer.cpp, build_htransfer_plan): builds
+tests/cpp/transfer_plan_check.cpp with that source, fe.cpp and mesh.cpp under ASan + UBSan (the library Makefile's
+transfer_plan_check target; the sanitizers are linked into that program only) and runs it as a child process on
 the smaller transfer cases of tests/hmg_cases.py and on one embedding that is a permutation of the fine elements.
 The program checks the owner bits, the children table, the tables and the coarse transposed map, replays Mult and
 MultTranspose from the plan in the device's order and checks every refusal of the plan builder; this test compares
@@ -30,14 +30,14 @@ def _hex(a):
 
 
 def test_htransfer_plans_replay_on_the_host(tmp_path):
-    exe = os.path.join(str(tmp_path), "htransfer_plan_check")
+    exe = os.path.join(str(tmp_path), "transfer_plan_check")
     subprocess.run(["make", "-s", "-C", PKG, f"OBJ={tmp_path}", exe], check=True, timeout=600)
     text, cases = [], []
     for name, p in CASES:
         P = HC.pair(name, p)
         xc, xf = P.inputs["random"]
         cases.append((name, p, P.ref(HR.LD), xc, xf))
-        text.append(f"case {p} {P.lf.ne} {P.lf.ndofs} {P.hf.ne} {P.hf.ndofs}\n" + _ints(P.lf.gather_map()) + "\n"
+        text.append(f"hcase {p} {P.lf.ne} {P.lf.ndofs} {P.hf.ne} {P.hf.ndofs}\n" + _ints(P.lf.gather_map()) + "\n"
                     + _ints(P.hf.gather_map()) + "\n" + _ints(P.parent) + "\n" + _ints(P.octant) + "\n" + _hex(xc) + "\n"
                     + _hex(xf) + "\n")
     # the fine elements permuted: the embedding is no longer (e / 8, corner e % 8), the owners change with it
@@ -46,7 +46,7 @@ def test_htransfer_plans_replay_on_the_host(tmp_path):
     gf, parent, octant = P.hf.gather_map()[perm], P.parent[perm], P.octant[perm]
     xc, xf = P.inputs["random"]
     cases.append(("moved322 permuted", 2, P.ref(HR.LD, gf, parent, octant), xc, xf))
-    text.append(f"case 2 {P.lf.ne} {P.lf.ndofs} {P.hf.ne} {P.hf.ndofs}\n" + _ints(P.lf.gather_map()) + "\n" + _ints(gf) + "\n"
+    text.append(f"hcase 2 {P.lf.ne} {P.lf.ndofs} {P.hf.ne} {P.hf.ndofs}\n" + _ints(P.lf.gather_map()) + "\n" + _ints(gf) + "\n"
                 + _ints(parent) + "\n" + _ints(octant) + "\n" + _hex(xc) + "\n" + _hex(xf) + "\n")
     r = subprocess.run([exe], input="".join(text) + "end\n", capture_output=True, text=True, timeout=300)
     print(r.stderr)

@@ -1,6 +1,7 @@
 """CPU test of the transfer operator's host construction (csrc/transfer.cpp): builds
 tests/cpp/transfer_plan_check.cpp with that source under ASan + UBSan (the library Makefile's transfer_plan_check
-target; the sanitizers are linked into that program only) and runs it as a child process on three meshes: a
+target, the one program that checks both kinds; the sanitizers are linked into that program only) and runs it as a
+child process on three meshes: a
 3 x 2 x 2 lattice, fichera.mesh's seven elements (shared faces with differing local orientations) and an
 SFC-ordered 4 x 4 x 4.  The program checks the owner bits and the coarse transposed map, replays Mult and
 MultTranspose from the plan, and this test compares what it prints with tests/mg_ref.py componentwise."""
@@ -35,7 +36,7 @@ def test_transfer_plans_replay_on_the_host(tmp_path):
             gc, gf = lf.gather_map(), hf.gather_map()
             xc, xf = rng.uniform(-1, 1, lf.ndofs), rng.uniform(-1, 1, hf.ndofs)
             cases.append((name, pc, pf, MR.Transfer(gc, lf.ndofs, pc, gf, hf.ndofs, pf, MR.LD), xc, xf))
-            text.append(f"case {lf.ne} {pc} {lf.ndofs} {pf} {hf.ndofs}\n" + " ".join(map(str, gc.reshape(-1))) + "\n"
+            text.append(f"pcase {lf.ne} {pc} {lf.ndofs} {pf} {hf.ndofs}\n" + " ".join(map(str, gc.reshape(-1))) + "\n"
                         + " ".join(map(str, gf.reshape(-1))) + "\n" + " ".join(float(v).hex() for v in xc) + "\n"
                         + " ".join(float(v).hex() for v in xf) + "\n")
     r = subprocess.run([exe], input="".join(text) + "end\n", capture_output=True, text=True, timeout=300)
