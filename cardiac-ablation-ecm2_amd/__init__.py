@@ -1059,6 +1059,16 @@ _PAR_SIGS = {
                                                                 ctypes.c_void_p, ctypes.c_int]),
     "ecm2_linear_form_info": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_int)] * 5),
     "ecm2_linear_form_destroy": (None, [ctypes.c_void_p]),
+    "ecm2_celldeath_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_void_p)]),
+    "ecm2_celldeath_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
+                                           ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]),
+    "ecm2_celldeath_measure": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
+                                              ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]),
+    "ecm2_celldeath_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                           ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "ecm2_celldeath_destroy": (None, [ctypes.c_void_p]),
 }
 
 
@@ -1849,3 +1859,72 @@ class LinearForm:
         v = [ctypes.c_int() for _ in range(5)]
         _check(_lib.ecm2_linear_form_info(self._h, *[ctypes.byref(a) for a in v]))
         return dict(zip(["ne", "ndofs", "d1d", "q1d", "n_integrators"], [a.value for a in v]))
+
+
+# ----------------------------------------------------------------------------
+# Cell death: the lesion state
+# ----------------------------------------------------------------------------
+CELLDEATH_THREE_STATE, CELLDEATH_ARRHENIUS = 0, 1
+
+
+class CellDeath:
+    """The cell-death state of n dofs on the device (include/ecm2_pa.h, "Cell death"; the application's model, not
+    the reference library's): fractions N (native), U (unfolded), D (dead) per dof with Arrhenius rates
+    k_i = A_i exp(-dE_i / (R (T + t_offset))), N' = -k1 N + k2 U, U' = k1 N - (k2 + k3) U, D' = k3 U.
+    CELLDEATH_THREE_STATE advances them by the exact propagator of a substep; CELLDEATH_ARRHENIUS is the classical
+    damage integral Omega (kept in U), D = 1 - exp(-Omega), and reads A[0], dE[0] alone.  A, dE: three values
+    each; t_offset = 273.15 for a field in degrees Celsius, 0 for kelvin.
+
+    Feeding the damage back into the operator needs no new coefficient kind: form 1 - D (a torch expression on
+    the state vector) and pass it as a GridFunctionCoefficient -- e.g. MassIntegrator(GridFunctionCoefficient(
+    gdt_cb_w0 * (1 - D))) beside the heat capacity's mass term scales perfusion to zero in dead tissue; the
+    coefficient's tensor is read at Assemble, so reassemble after the step."""
+
+    def __init__(self, model: int, A, dE, n: int, t_offset: float = 273.15):
+        A, dE = [float(v) for v in A], [float(v) for v in dE]
+        if len(A) != 3 or len(dE) != 3:
+            raise ECM2Error("CellDeath: A and dE hold three values each")
+        lib = _par_lib()
+        params = (ctypes.c_double * 6)(A[0], dE[0], A[1], dE[1], A[2], dE[2])
+        h = ctypes.c_void_p()
+        _check(lib.ecm2_celldeath_create(int(model), params, float(t_offset), int(n), ctypes.byref(h)))
+        self._h = h
+        self.n = int(n)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.ecm2_celldeath_destroy(self._h)
+            self._h = None
+
+    def _vec(self, t, name):
+        import torch
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.numel() != self.n:
+            raise ECM2Error(f"CellDeath: {name} must hold {self.n} float64 entries")
+        return _dev_ptr(t)
+
+    def Step(self, T0, dt, N, U, D, T1=None, nsub=1, check=False, stream=None):
+        """One step of length dt from the field T0 (and, with T1, towards the field at the end of the heat step:
+        substep m of nsub uses T0 + (m + 1/2) / nsub (T1 - T0)); N, U, D are updated in place.  All CUDA
+        float64 [n], 16-byte aligned (a view at an odd offset is refused), the temperatures distinct from the
+        state.  An entry whose T + t_offset is non-finite or <= 0 is left untouched; check=True reads their
+        number back (a synchronisation) and returns it, check=False returns None without one."""
+        count = ctypes.c_int(0)
+        _check(_lib.ecm2_celldeath_step(self._h, self._vec(T0, "T0"), self._vec(T1, "T1") if T1 is not None else None,
+                                        float(dt), int(nsub), self._vec(N, "N"), self._vec(U, "U"), self._vec(D, "D"),
+                                        ctypes.byref(count) if check else None, _stream(stream)))
+        return count.value if check else None
+
+    def Measure(self, D, w, theta, stream=None):
+        """(sum w D, sum w [D >= theta], sum w) in one deterministic pass; with w the LinearForm of the constant
+        1 these are the dead volume, the lesion volume and the domain's volume.  Synchronises."""
+        out = (ctypes.c_double * 3)()
+        _check(_lib.ecm2_celldeath_measure(self._h, self._vec(D, "D"), self._vec(w, "w"), float(theta), out,
+                                           _stream(stream)))
+        return tuple(out)
+
+    def info(self) -> dict:
+        model, n, off = ctypes.c_int(), ctypes.c_int(), ctypes.c_double()
+        params = (ctypes.c_double * 6)()
+        _check(_lib.ecm2_celldeath_info(self._h, ctypes.byref(model), ctypes.byref(n), params, ctypes.byref(off)))
+        return {"model": model.value, "n": n.value, "A": tuple(params[0::2]), "dE": tuple(params[1::2]),
+                "t_offset": off.value}

@@ -11,6 +11,7 @@
 #include "partition.hpp"
 #include "solvers.hpp"
 #include "transfer.hpp"
+#include "celldeath.hpp"
 
 #include <cstring>
 #include <memory>
@@ -56,6 +57,10 @@ struct ecm2_multigrid
 struct ecm2_linear_form
 {
    ecm2::LinearForm f;
+};
+struct ecm2_celldeath
+{
+   ecm2::CellDeath c;
 };
 
 namespace
@@ -1567,6 +1572,45 @@ int ecm2_linear_form_info(const ecm2_linear_form *lf, int *ne, int *ndofs, int *
 }
 
 void ecm2_linear_form_destroy(ecm2_linear_form *lf) { delete lf; }
+
+// ---- cell death: the lesion state (celldeath.hpp) ----
+int ecm2_celldeath_create(int model, const double params[6], double t_offset, int n, ecm2_celldeath **out)
+{
+   return guard([&] {
+      NEED(out);
+      *out = nullptr;
+      *out = new ecm2_celldeath{ecm2::CellDeath(model, params, t_offset, n)};
+   });
+}
+
+int ecm2_celldeath_step(ecm2_celldeath *h, const double *T0, const double *T1, double dt, int nsub, double *N, double *U,
+                        double *D, int *invalid, void *stream)
+{
+   return guard([&] { NEED(h); h->c.step(T0, T1, dt, nsub, N, U, D, invalid, S(stream)); });
+}
+
+int ecm2_celldeath_measure(ecm2_celldeath *h, const double *D, const double *w, double theta, double out[3],
+                           void *stream)
+{
+   return guard([&] { NEED(h); h->c.measure(D, w, theta, out, S(stream)); });
+}
+
+int ecm2_celldeath_info(const ecm2_celldeath *h, int *model, int *n, double params[6], double *t_offset)
+{
+   return guard([&] {
+      NEED(h);
+      const ecm2::CellDeathParams &p = h->c.params();
+      if (model) { *model = p.model; }
+      if (n) { *n = h->c.size(); }
+      if (params)
+      {
+         for (int i = 0; i < 3; i++) { params[2 * i] = p.A[i]; params[2 * i + 1] = p.dE[i]; }
+      }
+      if (t_offset) { *t_offset = p.t_offset; }
+   });
+}
+
+void ecm2_celldeath_destroy(ecm2_celldeath *h) { delete h; }
 
 int ecm2_par_form_timing(ecm2_par_form *f, int enable)
 {

@@ -1,5 +1,5 @@
 // dev_common.hpp -- device-side helpers shared by the gfx950 kernel translation units
-// (k_setup.hip, k_tpe.hip, k_line.hip, k_misc.hip, k_lform.hip, k_bdr.hip, k_conv.hip, k_pcg.hip, k_bicgstab.hip, k_cheb.hip, k_mg.hip, k_ess.hip, k_transfer.hip).  Included by .hip files only.
+// (k_setup.hip, k_tpe.hip, k_line.hip, k_misc.hip, k_lform.hip, k_bdr.hip, k_conv.hip, k_pcg.hip, k_bicgstab.hip, k_cheb.hip, k_mg.hip, k_ess.hip, k_transfer.hip, k_celldeath.hip).  Included by .hip files only.
 // (The solvers' 16-byte vector passes: vec_pass.hpp.)
 #pragma once
 

@@ -4,7 +4,8 @@
 // apply, restriction, index and one-thread-per-entry vector kernels; k_lform.hip: the linear form's element vectors;
 // k_bdr.hip: the boundary-face terms; k_conv.hip: the convection term; k_pcg.hip: the deterministic dot and the
 // device PCG's passes; k_bicgstab.hip: the BiCGSTAB loop's vector passes; k_cheb.hip: the Chebyshev smoother's; k_mg.hip: the multigrid cycle's; k_ess.hip: the essential elimination's; k_transfer.hip: the
-// transfer operator of both kinds, whose class is declared in transfer.hpp).
+// transfer operator of both kinds, whose class is declared in transfer.hpp; k_celldeath.hip: the cell-death state's,
+// declared in celldeath.hpp).
 //
 // Quadrature-data layouts (the qdata a PA form owns):
 //  * BLOCKED (fused thread-per-element kernel): elements in blocks of 64 (one

@@ -1,4 +1,4 @@
-// vec_pass.hpp -- the 16-byte vector passes of the device solvers (k_pcg.hip, k_cheb.hip, k_mg.hip, k_bicgstab.hip, k_ess.hip):
+// vec_pass.hpp -- the 16-byte vector passes of the device solvers (k_pcg.hip, k_cheb.hip, k_mg.hip, k_bicgstab.hip, k_ess.hip) and of the cell-death state (k_celldeath.hip):
 // an FP64 vector is read and written two entries at a time, and one thread takes entry n - 1 of an odd n.  A pass
 // states its arithmetic per entry once, as a body `[&](auto k) { ... }` that reaches its vectors through ld / st /
 // dot_acc only: called with a Pair it works on v2d, called with an Entry on double, the same operations in the same

@@ -728,6 +728,68 @@ int ecm2_linear_form_info(const ecm2_linear_form *lf, int *ne, int *ndofs, int *
 void ecm2_linear_form_destroy(ecm2_linear_form *lf);
 
 /* ------------------------------------------------------------------------ */
+/* Cell death: the lesion state on the device                                 */
+/* ------------------------------------------------------------------------ */
+/* The last stage of an ablation simulation: which tissue died.  The model is the application's, not the
+ * reference library's, so nothing here cites it; this comment is the model's statement.
+ *
+ * State.  Each dof holds three fractions N (native), U (unfolded, still reversible) and D (dead),
+ * N + U + D = 1.
+ * Rates.  k_i(T) = A_i exp(-dE_i / (R T_K)), i = 1..3, R = 8.31446261815324 J/(mol K), T_K = T + t_offset
+ * (a field in degrees Celsius: t_offset = 273.15; a kelvin field: 0); A_i >= 0 [1/s] and dE_i >= 0 [J/mol] are
+ * the caller's (A_i <= 1e150: the discriminant below squares the rates).
+ * Kinetics.  N' = -k1 N + k2 U,  U' = k1 N - (k2 + k3) U,  D' = k3 U.
+ *
+ * ECM2_CELLDEATH_THREE_STATE: over a step of length dt with T frozen the update is the exact propagator of this
+ * linear system -- not an ODE scheme: no stability limit, and a step of dt equals two steps of dt / 2.  The
+ * eigenvalues are real and non-positive: with a, b, c = k1, k2, k3 and sigma = a + b + c the discriminant is
+ * (2 delta)^2 = (a - c)^2 + b^2 + 2 b (a + c), lambda_- = -(sigma / 2 + delta), lambda_+ = a c / lambda_-.
+ *   exp(M dt) = e^{lambda_- dt} I + g (M - lambda_- I),  g = e^{lambda_+ dt} (-expm1(-2 delta dt)) / (2 delta)
+ * (no sinh: nothing overflows at 95 C and dt = 300 s); every quotient takes its limit where its denominator is
+ * zero, so an entry whose rates are all zero (A_i = 0, or T_K so small that the exponentials underflow) is left
+ * bitwise unchanged, and any single A_i = 0 works.  D is never recomputed as 1 - N - U: it advances by
+ * dD = k3 int U dt >= 0 (through psi(l) = expm1(l dt) / l and G = (psi(lambda_+) - psi(lambda_-)) / (2 delta),
+ * taken in the equal form (g - psi(lambda_-)) / lambda_+ wherever |lambda_+| >= 2 delta, so that nothing is divided
+ * by a small 2 delta near a double eigenvalue), clamped at 0 from below, so D never decreases and N, U >= 0.  The
+ * absolute error of every fraction is a few u (1 + dE / (R T_K)) per step; the relative error of a
+ * small increment dD is not bounded.  rate * dt may overflow: everything then dies, nothing turns NaN.
+ *
+ * ECM2_CELLDEATH_ARRHENIUS: the classical one-integral damage, Omega += dt A_1 exp(-dE_1 / (R T_K)), stored in
+ * U; D = 1 - exp(-Omega) (formed with expm1, never below the D passed in), N = 1 - D.  Only A_1, dE_1 are read.
+ *
+ * Temperature over the step.  The caller passes T0 and optionally T1, the field at the start and at the end of
+ * the heat step, and nsub >= 1: substep m of length dt / nsub uses T0 + (m + 1/2) / nsub (T1 - T0); T1 == NULL
+ * freezes T0 for every substep.  An entry whose T_K is non-finite or <= 0 at any substep is left unchanged and
+ * counted. */
+#define ECM2_CELLDEATH_THREE_STATE 0
+#define ECM2_CELLDEATH_ARRHENIUS 1
+typedef struct ecm2_celldeath ecm2_celldeath;
+/* A state of n entries (one rank's dofs: the update is per dof, a distributed caller makes one per rank).
+ * An unknown model, a negative or non-finite parameter, A_i > 1e150, a non-finite t_offset or n < 1:
+ * ECM2_ERR_ARG, before a device is asked for; without a device: ECM2_ERR_HIP. */
+int ecm2_celldeath_create(int model, const double params[6] /* A1, dE1, A2, dE2, A3, dE3 */, double t_offset, int n,
+                          ecm2_celldeath **out);
+/* One step: N, U, D (device [n]) in place from T0 and T1 (device [n]; T1 NULL: T0 frozen).  Checked before
+ * anything is enqueued (ECM2_ERR_ARG): nsub < 1; a negative or non-finite dt; a vector that is not 16-byte
+ * aligned (two entries per access, as ecm2_operator_bicgstab's x); T0 or T1 overlapping a state vector; state
+ * vectors that overlap.  dt = 0 is the identity.  invalid (host, optional) receives the number of entries left
+ * unchanged for their T_K; reading it back synchronises the stream, NULL does not (and is what a captured
+ * stream needs).  No atomics: two steps on the same inputs are bitwise equal.  One handle serves one stream
+ * at a time (it owns the partial sums' workspace). */
+int ecm2_celldeath_step(ecm2_celldeath *h, const double *T0, const double *T1 /* NULL */, double dt, int nsub,
+                        double *N, double *U, double *D, int *invalid /* NULL: not read back, no sync */,
+                        void *stream);
+/* out (host) = sum_i w_i D_i, sum_i w_i [D_i >= theta], sum_i w_i in one read of w and D (device [n], 16-byte
+ * aligned).  With w the assembled linear form of the constant 1 (ecm2_linear_form_assemble) these are the dead
+ * volume, the lesion volume and |Omega|.  Two-pass, a fixed summation order (bitwise reproducible);
+ * synchronises the stream.  Across ranks the caller adds the ranks' sums (with w zeroed on dofs it does not own). */
+int ecm2_celldeath_measure(ecm2_celldeath *h, const double *D, const double *w, double theta, double out[3],
+                           void *stream);
+/* Introspection (any output may be NULL). */
+int ecm2_celldeath_info(const ecm2_celldeath *h, int *model, int *n, double params[6], double *t_offset);
+void ecm2_celldeath_destroy(ecm2_celldeath *h);
+
+/* ------------------------------------------------------------------------ */
 /* Distributed form: ParBilinearForm / RAPOperator(P, A, P) over RCCL          */
 /* ------------------------------------------------------------------------ */
 typedef struct ecm2_partition ecm2_partition;
